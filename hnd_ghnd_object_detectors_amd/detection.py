@@ -169,8 +169,7 @@ class RpnEngine(object):
     def __init__(self, head):
         self.head = head
         self.wc3 = E.WeightCache(head.conv.weight)
-        tile = E.use_winograd(head.conv.weight.shape[1], head.conv.weight.shape[0], 1)
-        self.wino = E.WinoCache(head.conv.weight, tile) if tile else None
+        self.tile = E.use_winograd(head.conv.weight.shape[1], head.conv.weight.shape[0], 1)     # 0: direct
         self.bufs = None
         self.plan_key = None
         self.merged = None
@@ -197,12 +196,11 @@ class RpnEngine(object):
         if self.bufs is None:
             self.bufs = E.Buffers(feats[0].device)
         _, w1, b1, pk1 = self._merged_1x1()
-        if self.wino is not None:
-            self.wino.get(False)
-            self.wino.refresh()
+        if self.tile:
+            self.wc3.wino(False, self.tile)
         else:
             self.wc3.get()
-            self.wc3.refresh()
+        self.wc3.refresh()
         key = tuple((f.data_ptr(), tuple(f.shape)) for f in feats) + (self.head.conv.bias.data_ptr(),)
         if key != self.plan_key:
             self.plan, self.outs = [], []
@@ -214,11 +212,11 @@ class RpnEngine(object):
                 t = self.bufs.get('t%d' % i, (n, h, w, c))
                 o = self.bufs.get('o%d' % i, (n, h, w, ldc))
                 bias3 = self.head.conv.bias.detach()
-                if self.wino is not None:
-                    nv, nm = ops.WinoConv.scratch_elems(n, h, w, c, c, E.WINOGRAD)
+                if self.tile:
+                    nv, nm = ops.WinoConv.scratch_elems(n, h, w, c, c, self.tile)
                     need = (max(need[0], nv), max(need[1], nm))
                     v, m = self.bufs.get('wino_v', (need[0],)), self.bufs.get('wino_m', (need[1],))
-                    self.plan += ops.WinoConv(f, self.wino.get(False), t, v, m, epi_shift=bias3,
+                    self.plan += ops.WinoConv(f, self.wc3.wino(False, self.tile), t, v, m, epi_shift=bias3,
                                               relu=True).launches('rpn.conv%d' % i)
                 else:
                     self.plan.append((ops.conv_forward(f, self.wc3.get(), t, 3, 1, 1, epi_shift=bias3, relu=True),
@@ -518,14 +516,10 @@ class RoIHeads(nn.Module):
             cout = conv.weight.shape[0]
             y = torch.empty((k, h, w, cout), dtype=torch.float32, device=x.device)
             tile = E.use_winograd(cin, cout, 1)
+            wc = self._cache((tag, i), conv.weight)
             if tile:
-                if self._wc is None:
-                    self._wc = {}
-                wn = self._wc.get((tag, i, 'wino'))
-                if wn is None or wn.weight is not conv.weight:
-                    wn = self._wc[(tag, i, 'wino')] = E.WinoCache(conv.weight, tile)
-                ww = wn.get(False)
-                wn.refresh()
+                ww = wc.wino(False, tile)
+                wc.refresh()
                 nv, nm = ops.WinoConv.scratch_elems(k, h, w, cin, cout, tile)
                 v = torch.empty(nv, dtype=torch.float32, device=x.device)
                 m = torch.empty(nm, dtype=torch.float32, device=x.device)
@@ -533,7 +527,6 @@ class RoIHeads(nn.Module):
                                          relu=True).launches('%s.conv%d' % (tag, i)):
                     E._run(l, t)
             else:
-                wc = self._cache((tag, i), conv.weight)
                 pk = wc.get()
                 wc.refresh()
                 E._run(ops.conv_forward(x, pk, y, 3, 1, 1, epi_shift=conv.bias.detach(), relu=True),

@@ -106,80 +106,47 @@ class FrozenAffine(object):
 
 
 class WeightCache(object):
-    """Packed GEMM operands of one conv weight; frozen weights are packed once, trainable ones every step."""
+    """Every packed GEMM operand of one conv weight -- direct packs (get) and Winograd-domain ones (wino, wino2) -- in one
+    dict under one version.  An operand's buffer address is stable for the life of the cache (prebuilt launch
+    descriptors point at it); refresh() re-packs all of them into their own buffers.  Frozen weights are packed once,
+    trainable ones every step."""
 
     def __init__(self, weight):
-        self.weight = weight
-        self.packs = {}
-        self.ver = None
+        self.weight, self.packs, self.ver = weight, {}, None
 
-    def get(self, transposed=False, chan_pad=None, taps=None, kscale=None):
-        """the PackedWeight for this layout; its buffer address is stable for the life of the cache (prebuilt
-        launch descriptors point at it), refresh() re-runs the pack kernel into the same buffer.
-        kscale: per-channel scale folded into the K operand (ops.pack_weights); a NEW scale tensor (the FrozenBN fold
-        was refreshed) re-packs into the same buffer."""
-        key = (transposed, chan_pad, taps, kscale is not None)
+    def _pack(self, key, make):
         pk = self.packs.get(key)
         if pk is None:
-            pk = ops.pack_weights(self.weight.detach(), transposed, chan_pad, taps, kscale=kscale)
-            self.packs[key] = pk
-        elif kscale is not None and pk.kscale is not kscale:
+            if not self.packs:      # (made later, while older operands are stale: the next refresh re-packs them all)
+                self.ver = weight_version(self.weight)
+            pk = self.packs[key] = make(self.weight.detach())
+        return pk
+
+    def get(self, transposed=False, chan_pad=None, taps=None, kscale=None):
+        """the direct pack for this layout (ops.pack_weights).  kscale: per-channel scale folded into the K operand; a
+        NEW scale tensor (the FrozenBN fold was refreshed) re-packs into the same buffer."""
+        pk = self._pack((transposed, chan_pad, taps, kscale is not None),
+                        lambda w: ops.pack_weights(w, transposed, chan_pad, taps, kscale=kscale))
+        if kscale is not None and pk.kscale is not kscale:
             pk.kscale = kscale
             pk.repack()
         return pk
 
+    def wino(self, dgrad=False, tile=2):
+        """ops.WinoWeights of a 3x3 conv for the output tile the launch uses (wino_tile_for picks it per geometry)"""
+        return self._pack(('wino', dgrad, tile), lambda w: ops.WinoWeights(w, dgrad, tile))
+
+    def wino2(self, dgrad=False, tile=4):
+        """ops.Wino2Weights of a 2x2 head conv"""
+        return self._pack(('wino2', dgrad, tile), lambda w: ops.Wino2Weights(w, dgrad, tile))
+
     def refresh(self, force=False):
-        """re-run the pack kernels if the parameter changed (or always, for trainable weights)."""
+        """re-pack every operand if the parameter changed, or always with force (trainable weights)"""
         ver = weight_version(self.weight)
         if force or ver != self.ver:
             for pk in self.packs.values():
                 pk.src = self.weight.detach()
                 pk.repack()
-            self.ver = ver
-
-
-class WinoCache(object):
-    """Winograd-domain weights (forward and transposed) of one frozen 3x3 conv, transformed once per version."""
-
-    def __init__(self, weight, tile):
-        self.weight, self.tile, self.packs, self.ver = weight, tile, {}, None
-
-    def get(self, dgrad=False, tile=None):
-        """tile: the output tile the launch will use (wino_tile_for picks it per geometry); default = the cache's own"""
-        tile = tile or self.tile
-        ww = self.packs.get((dgrad, tile))
-        if ww is None:
-            ww = self.packs[(dgrad, tile)] = ops.WinoWeights(self.weight.detach(), dgrad, tile)
-            self.ver = weight_version(self.weight)
-        return ww
-
-    def refresh(self):
-        ver = weight_version(self.weight)
-        if ver != self.ver:
-            for ww in self.packs.values():
-                ww.src = self.weight.detach()
-                ww.repack()
-            self.ver = ver
-
-
-class Wino2Cache(object):
-    """F(4x4,2x2) weights (forward / transposed) of one head conv; trainable, so re-transformed every step."""
-
-    def __init__(self, weight):
-        self.weight, self.packs, self.ver = weight, {}, None
-
-    def get(self, dgrad=False, tile=4):
-        ww = self.packs.get((dgrad, tile))
-        if ww is None:
-            ww = self.packs[(dgrad, tile)] = ops.Wino2Weights(self.weight.detach(), dgrad, tile)
-        return ww
-
-    def refresh(self, force=False):
-        ver = weight_version(self.weight)
-        if force or ver != self.ver:
-            for ww in self.packs.values():
-                ww.src = self.weight.detach()
-                ww.repack()
             self.ver = ver
 
 
@@ -414,7 +381,7 @@ class StemEngine(object):
 
 # =========================================================================================== frozen layers
 class _Block(object):
-    __slots__ = ('mod', 'stride', 'has_ds', 'planes', 'cin', 'w1', 'w2', 'w3', 'wd', 'f1', 'f2', 'f3', 'fd', 'wino')
+    __slots__ = ('mod', 'stride', 'has_ds', 'planes', 'cin', 'w1', 'w2', 'w3', 'wd', 'f1', 'f2', 'f3', 'fd', 'wino_tile')
 
 
 class FrozenLayerEngine(object):
@@ -432,8 +399,7 @@ class FrozenLayerEngine(object):
             b.f1, b.f2, b.f3 = FrozenAffine(m.bn1), FrozenAffine(m.bn2), FrozenAffine(m.bn3)
             b.wd = WeightCache(m.downsample[0].weight) if b.has_ds else None
             b.fd = FrozenAffine(m.downsample[1]) if b.has_ds else None
-            tile = use_winograd(b.planes, b.planes, b.stride)
-            b.wino = WinoCache(m.conv2.weight, tile) if tile else None
+            b.wino_tile = use_winograd(b.planes, b.planes, b.stride)        # 0: conv2 is a direct launch
             self.blocks.append(b)
         self.bufs = None
         self.plan_key = None
@@ -479,11 +445,10 @@ class FrozenLayerEngine(object):
         affs = [(b.f1.get(), b.f2.get(), b.f3.get(), b.fd.get() if b.has_ds else None) for b in self.blocks]
         for b in self.blocks:
             for wc in (b.w1, b.w2, b.w3, b.wd):
-                if wc is not None and not (wc is b.w2 and b.wino is not None):
-                    wc.get()
+                if wc is not None:
+                    if not (wc is b.w2 and b.wino_tile):    # (Winograd packs are made by the plans, for the tile the
+                        wc.get()                            # geometry picks)
                     wc.refresh()
-            if b.wino is not None:          # (its packs are made by the plans, for the tile the geometry picks)
-                b.wino.refresh()
         self._out_buf = self.out_provider(self.out_shape(x)) if self.out_provider is not None else None
         key = (x.data_ptr(), tuple(x.shape), keep, getattr(self, 'for_backward', True),
                tuple(a[0][0].data_ptr() for a in affs), None if self._out_buf is None else self._out_buf.data_ptr())
@@ -527,11 +492,11 @@ class FrozenLayerEngine(object):
                     and b.planes % 128 == 0):
                 a2b = self.bufs.get('a2bits_' + sfx, tuple(a2.shape[:3]) + (a2.shape[3] // 4,), torch.uint8)
             bits_step = a2b is not None
-            if b.wino is not None:      # stride-1 3x3, >= 256 channels: Winograd F(2x2,3x3)
-                tile = wino_tile_for(b.wino.tile, n, h, w)
+            if b.wino_tile:             # stride-1 3x3, >= 256 channels: Winograd F(2x2,3x3)
+                tile = wino_tile_for(b.wino_tile, n, h, w)
                 v, m = self._wino_scratch(n, h, w, b.planes, b.planes, tile)
                 in_transform = a2b is not None and tile in (4, 6)
-                self.fwd += ops.WinoConv(a1, b.wino.get(False, tile), a2, v, m, epi_scale=a2f[0], epi_shift=a2f[1],
+                self.fwd += ops.WinoConv(a1, b.w2.wino(False, tile), a2, v, m, epi_scale=a2f[0], epi_shift=a2f[1],
                                          relu=True, mask_out=a2b if in_transform else None).launches(tagp + '.conv2')
                 bits_step = bits_step and not in_transform
             else:
@@ -627,10 +592,10 @@ class FrozenLayerEngine(object):
             ls, _ = ops.conv_dgrad(g, b.w3, g_a2, 1, 1, 0, **mk3, **fold(s3))
             self.bwd += [(l, tagp + '.conv3.dgrad') for l in ls]
             # conv2 (3x3, stride s): g_a1 = [a1>0] * dgrad(g_a2 * s2)
-            if b.wino is not None:
-                tile = wino_tile_for(b.wino.tile, n, h, w)
+            if b.wino_tile:
+                tile = wino_tile_for(b.wino_tile, n, h, w)
                 v, m = self._wino_scratch(n, h, w, b.planes, b.planes, tile)
-                self.bwd += ops.WinoConv(g_a2, b.wino.get(True, tile), g_a1, v, m, pro_scale=s2,
+                self.bwd += ops.WinoConv(g_a2, b.w2.wino(True, tile), g_a1, v, m, pro_scale=s2,
                                          mask=a1).launches(tagp + '.conv2.dgrad')
             else:
                 ls, _ = ops.conv_dgrad(g_a2, b.w2, g_a1, 3, b.stride, 1, mask=a1, **fold(s2))
@@ -663,7 +628,7 @@ class FrozenLayerEngine(object):
 
 # =========================================================================================== student head
 class _HeadConv(object):
-    __slots__ = ('conv', 'bn', 'pad', 'relu', 'cin', 'cout', 'cs_in', 'cs_out', 'wc', 'wino', 'wino_f', 'wino_d', 'wino_w')
+    __slots__ = ('conv', 'bn', 'pad', 'relu', 'cin', 'cout', 'cs_in', 'cs_out', 'wc', 'wino_f', 'wino_d', 'wino_w')
 
 
 class HeadEngine(object):
@@ -691,7 +656,6 @@ class HeadEngine(object):
             ok = bool(WINOGRAD and WINOGRAD_HEAD and 512 % hc.cout == 0)
             hc.wino_f = ok and (deep or (WINOGRAD2_6 and hc.cin >= 256 and hc.cout == 64))
             hc.wino_d = ok and (deep or (WINOGRAD2_6 and hc.cin == 64 and hc.cout >= 256))
-            hc.wino = Wino2Cache(conv.weight) if (hc.wino_f or hc.wino_d) else None
             #   * 64 -> 256 (encoder conv1), round 4: the WEIGHT gradient in the Winograd domain as well, on an input
             #     transform of its own made in the backward pass (the forward stays direct): 2.9x fewer multiplies than
             #     the direct weight gradient (1.31 -> ~0.6 ms), and with both consumers of dy on transforms the BatchNorm
@@ -723,11 +687,9 @@ class HeadEngine(object):
         ops.pack_batch_begin()              # the ~28 operand re-packs of a training step go out as one launch
         try:
             for hc in self.layers:
-                if hc.wino is not None:         # (packs are made by the plan, for the tile its geometry picks)
-                    hc.wino.refresh(force=training)
-                if not hc.wino_f:
+                if not hc.wino_f:               # (Winograd packs are made by the plan, for the tile its geometry picks)
                     hc.wc.get(False, hc.cs_in)
-                hc.wc.refresh(force=training)            # forward / transposed / wgrad-side packs, whichever were made
+                hc.wc.refresh(force=training)   # forward / transposed / wgrad-side / Winograd packs, whichever were made
         finally:
             ops.pack_batch_end()
         ptrs = tuple(t.data_ptr() for hc in self.layers
@@ -792,7 +754,7 @@ class HeadEngine(object):
                     v = b.get('wino_keep_v%d' % i,
                               (ops.Wino2Conv.scratch_elems(n, oh, ow, hc.cs_in, hc.cs_out, t2)[0],))
                 with ops.emulation_unless(i in BX3_HEAD_FWD):
-                    wl = ops.Wino2Conv(cur, hc.wino.get(False, t2), y, v, mm, hc.pad, pro_scale=cur_scale,
+                    wl = ops.Wino2Conv(cur, hc.wc.wino2(False, t2), y, v, mm, hc.pad, pro_scale=cur_scale,
                                        pro_shift=cur_shift, pro_relu=cur_relu, stats=st)
                 self.wino_fwd[i] = wl
                 self.convs.append(wl.launches('layer1.conv%d' % i))
@@ -851,8 +813,6 @@ class HeadEngine(object):
         if not hasattr(self, 'parts'):
             self.parts = {}
         for hc in self.layers[lo:hi]:
-            if hc.wino is not None:
-                hc.wino.refresh()
             if not hc.wino_f:
                 hc.wc.get(False, hc.cs_in)
             hc.wc.refresh()
@@ -879,7 +839,7 @@ class HeadEngine(object):
                 if hc.wino_f:                    # same arithmetic as the unsplit model
                     t2 = wino2_tile_for(oh, ow)
                     v, mm = self._wino_scratch(n, oh, ow, hc.cs_in, hc.cs_out, t2)
-                    plan['convs'] += ops.Wino2Conv(cur, hc.wino.get(False, t2), y, v, mm, hc.pad, pro_scale=pro[0],
+                    plan['convs'] += ops.Wino2Conv(cur, hc.wc.wino2(False, t2), y, v, mm, hc.pad, pro_scale=pro[0],
                                                    pro_shift=pro[1], pro_relu=pro[2]).launches(tag)
                 else:
                     plan['convs'].append((ops.conv_forward(cur, hc.wc.get(False, hc.cs_in), y, 2, 1, hc.pad,
@@ -1068,7 +1028,7 @@ class HeadEngine(object):
                     bwd_stats = (self.y[i - 1], self.scale[i - 1], self.shift[i - 1], self.mean[i - 1],
                                  self.rstd[i - 1], prev.relu, part)
                     self.bsteps[i - 1]['folded'] = (part, nblk)
-                dg_obj = ops.Wino2Conv(gbuf[i], hc.wino.get(True, t2), tgt, v, mm, 1 - hc.pad, bwd_stats=bwd_stats)
+                dg_obj = ops.Wino2Conv(gbuf[i], hc.wc.wino2(True, t2), tgt, v, mm, 1 - hc.pad, bwd_stats=bwd_stats)
                 st['dgrad'] = dg_obj.launches('layer1.conv%d.dgrad' % i)
                 flops += 2 * npix * hc.cout * 4 * hc.cin
             elif tgt is not None:
@@ -1113,8 +1073,7 @@ class FpnEngine(object):
     def __init__(self, inner_blocks, layer_blocks):
         self.inner = [(m, WeightCache(m.weight)) for m in inner_blocks]
         self.layer = [(m, WeightCache(m.weight)) for m in layer_blocks]
-        self.wino = [WinoCache(m.weight, use_winograd(m.weight.shape[1], m.weight.shape[0], 1))
-                     if use_winograd(m.weight.shape[1], m.weight.shape[0], 1) else None for m in layer_blocks]
+        self.wino = [use_winograd(m.weight.shape[1], m.weight.shape[0], 1) for m in layer_blocks]    # tiles, 0: direct
         self.bufs = None
         self.plan_key = None
         self.flops_fwd = 0
@@ -1124,10 +1083,8 @@ class FpnEngine(object):
         if self.bufs is None:
             self.bufs = Buffers(feats[0].device)
         for i, (m, wc) in enumerate(self.inner + self.layer):
-            if i >= len(self.inner) and self.wino[i - len(self.inner)] is not None:
-                self.wino[i - len(self.inner)].refresh()      # (packs are made by the plan, per level geometry)
-                continue
-            wc.get()
+            if not (i >= len(self.inner) and self.wino[i - len(self.inner)]):
+                wc.get()                # (Winograd packs are made by the plan, per level geometry)
             wc.refresh()
         key = tuple((f.data_ptr(), tuple(f.shape)) for f in feats) + \
             tuple(m.bias.data_ptr() for m, _ in self.inner + self.layer)
@@ -1141,7 +1098,7 @@ class FpnEngine(object):
             n0, h0, w0, _ = feats[0].shape
             oc = self.layer[0][0].weight.shape[0]
             need = (ops.WinoConv.scratch_elems(n0, h0, w0, oc, oc, wino_tile_for(WINOGRAD, n0, h0, w0))
-                    if any(w is not None for w in self.wino) else (0, 0))
+                    if any(self.wino) else (0, 0))
             for i in range(nlev - 1, -1, -1):
                 f = feats[i]
                 n, h, w, c = f.shape
@@ -1152,12 +1109,12 @@ class FpnEngine(object):
                                                   res1=up, res1_up=up is not None), 'fpn.inner%d' % i))
                 ml, wl = self.layer[i]
                 self.results[i] = self.bufs.get('p%d' % i, (n, h, w, ml.weight.shape[0]))
-                if self.wino[i] is not None:            # 3x3 256->256 output conv: Winograd F(2x2,3x3)
-                    tile = wino_tile_for(self.wino[i].tile, n, h, w)
+                if self.wino[i]:                        # 3x3 256->256 output conv: Winograd F(2x2,3x3)
+                    tile = wino_tile_for(self.wino[i], n, h, w)
                     nv, nm = ops.WinoConv.scratch_elems(n, h, w, ml.weight.shape[1], ml.weight.shape[0], tile)
                     need = (max(nv, need[0]), max(nm, need[1]))
                     v, mm = self.bufs.get('wino_v', (need[0],)), self.bufs.get('wino_m', (need[1],))
-                    self.fwd += ops.WinoConv(inner[i], self.wino[i].get(False, tile), self.results[i], v, mm,
+                    self.fwd += ops.WinoConv(inner[i], wl.wino(False, tile), self.results[i], v, mm,
                                              epi_shift=ml.bias.detach()).launches('fpn.layer%d' % i)
                 else:
                     self.fwd.append((ops.conv_forward(inner[i], wl.get(), self.results[i], 3, 1, 1,
@@ -1194,11 +1151,11 @@ class FpnEngine(object):
                 have = False
                 if i in term_grads:
                     ml, wl = self.layer[i]
-                    if self.wino[i] is not None:
-                        tile = wino_tile_for(self.wino[i].tile, n, h, w)
+                    if self.wino[i]:
+                        tile = wino_tile_for(self.wino[i], n, h, w)
                         nv, nm = ops.WinoConv.scratch_elems(n, h, w, c, c, tile)
                         v, mm = self.bufs.get('wino_v_bwd', (nv,)), self.bufs.get('wino_m_bwd', (nm,))
-                        self.bwd += ops.WinoConv(term_grads[i], self.wino[i].get(True, tile), g_inner, v,
+                        self.bwd += ops.WinoConv(term_grads[i], wl.wino(True, tile), g_inner, v,
                                                  mm).launches('fpn.layer%d.dgrad' % i)
                     else:
                         ls, _ = ops.conv_dgrad(term_grads[i], wl, g_inner, 3, 1, 1)

@@ -47,11 +47,12 @@ def device_arch():
 
 # --------------------------------------------------------------------------------------- weights
 # fp32 EMULATED on the bf16 matrix pipe (csrc/conv_bx3.hip) is the DEFAULT for the launches it covers since round 6
-# (VERDICT r5 item 1): every packed operand the kernel can use gets a three-plane bf16 image, and a launch carries it when
-# hnd_bf16x3_recommended says so for its LAYER (rows one image contributes, depth, output channels -- never the batch).
+# (VERDICT r5 item 1): a launch carries a three-plane bf16 image of its packed operand when hnd_bf16x3_recommended says so
+# for its LAYER (rows one image contributes, depth, output channels -- never the batch).
 # Covered launches compute with fp32-level accuracy (0.8x the native kernel's error against fp64) but NOT the fp32 kernels'
 # bits.  HND_BF16X3=0: no image anywhere, native fp32 MFMA everywhere (the `value_native_fp32` leg of bench.py).
-#   mode 'policy' (default) / 'off' / 'force' (tests: attach whenever an image exists, whatever the policy says)
+#   mode 'policy' (default) / 'off' / 'force' (tests: attach an image whenever the operand can have one, whatever the
+#   policy says) / 'bx3' / 'bxs' (force that one family, attach no image of the other).  Read by conv_desc only.
 BX3_MODE = ['policy' if os.environ.get('HND_BF16X3', '1') != '0' else 'off']
 
 
@@ -60,11 +61,11 @@ def bx3_on():
 
 
 class emulation(object):
-    """with ops.emulation('off' | 'force' | 'policy'): ... -- launches and packed operands BUILT inside take that mode
-    (tests hold the native and the emulated family side by side with it)."""
+    """with ops.emulation('off' | 'policy' | 'force' | 'bx3' | 'bxs'): ... -- launches BUILT inside take that mode (tests
+    hold the native and the emulated family side by side with it)."""
 
     def __init__(self, mode):
-        assert mode in ('policy', 'off', 'force'), mode
+        assert mode in ('policy', 'off', 'force', 'bx3', 'bxs'), mode
         self.mode = mode
 
     def __enter__(self):
@@ -91,81 +92,116 @@ def bx3_recommended(rows_per_image, kdim, cout):
     return bool(_L.hnd_bf16x3_recommended(int(rows_per_image), int(kdim), int(cout)))
 
 
-def bx3_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=False):
-    """(re)build the bf16x3 image of a packed fp32 operand; None when the emulation is off (unless `force`: tests) or
-    cannot use this operand"""
-    if not (bx3_on() or force) or (kdim != 128 and (kdim % 256 != 0 or kdim > 2048)) or rows_pad % 64 != 0:
-        return None
-    n = int(_L.hnd_pack_bf16x3_elems(rows_pad, kdim, groups))
-    if out is None or out.numel() != n:
-        out = torch.empty(n, dtype=torch.int16, device=buf.device)
+# The two image builders take a packed fp32 buffer and (re)build its image into `out`, or into a new tensor.  An image no
+# longer depends on the emulation mode: `force` is accepted for callers written when it did, and changes nothing.
+def bx3_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=None):
+    """the bf16x3 image (hnd_pack_bf16x3: the B-resident emulation kernel, csrc/conv_bx3.hip)"""
+    if out is None:
+        out = torch.empty(int(_L.hnd_pack_bf16x3_elems(rows_pad, kdim, groups)), dtype=torch.int16, device=buf.device)
     check(_L.hnd_pack_bf16x3(buf.data_ptr(), out.data_ptr(), rows_pad, kdim, groups, int(group_stride), stream_ptr()),
           'hnd_pack_bf16x3')
     return out
 
 
-def bxs_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=False):
-    """(re)build the STREAM image (hnd_pack_bf16x3s: the B-streamed emulation kernel, csrc/conv_bxs.hip) of a packed fp32
-    operand; None when the emulation is off (unless `force`) or the kernel cannot use this operand"""
-    if not (bx3_on() or force) or kdim % 128 != 0 or rows_pad % 64 != 0:
-        return None
-    n = int(_L.hnd_pack_bf16x3s_elems(rows_pad, kdim, groups))
-    if out is None or out.numel() != n:
-        out = torch.empty(n, dtype=torch.int16, device=buf.device)
+def bxs_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=None):
+    """the STREAM image (hnd_pack_bf16x3s: the B-streamed emulation kernel, csrc/conv_bxs.hip)"""
+    if out is None:
+        out = torch.empty(int(_L.hnd_pack_bf16x3s_elems(rows_pad, kdim, groups)), dtype=torch.int16, device=buf.device)
     check(_L.hnd_pack_bf16x3s(buf.data_ptr(), out.data_ptr(), rows_pad, kdim, groups, int(group_stride), stream_ptr()),
           'hnd_pack_bf16x3s')
     return out
 
 
 class PackedWeight(object):
-    """K-contiguous GEMM operand made by hnd_pack_weights."""
-    __slots__ = ('buf', 'rows', 'kdim', 'ni', 'nj', 'chan_pad', 'chan_real', 'src', 'args', 'kscale', 'bx3', 'bxs',
-                 'used3', 'useds')
+    """A GEMM weight operand: `groups` fp32 matrices [rows_pad][kdim] (K contiguous), `group_stride` floats apart in `buf`;
+    K holds `taps` taps of chan_pad channels (chan_real of them real).  The subclasses fill `buf` from a conv weight
+    (pack_weights, WinoWeights, Wino2Weights); a PackedWeight itself wraps a buffer its caller filled.
+
+    The pre-split bf16 images of the emulation kernels (bx3, bxs) are made when a launch descriptor first asks for one
+    (attach) and from then on re-made in place by every repack(), for as long as the operand lives.  An image set from
+    outside (bx3_image) is the one a launch gets, and re-packs refresh it too."""
+    groups, group_stride, taps, bx3, bxs = 1, 0, 1, None, None          # an ungrouped, tap-free operand without images
+
+    def __init__(self, buf, rows, kdim, chan_pad, chan_real=None, groups=1, group_stride=0, taps=1):
+        self.buf, self.rows, self.rows_pad, self.kdim = buf, rows, round_up(rows, 64), kdim
+        self.chan_pad, self.chan_real = chan_pad, chan_pad if chan_real is None else chan_real
+        self.groups, self.group_stride, self.taps = groups, group_stride, taps
+        self.bx3 = self.bxs = None
+
+    def fill(self):
+        """(re)compute buf from the source weight (nothing to do for a buffer the caller filled)"""
 
     def repack(self):
-        if PACK_BATCH['open'] and getattr(self, 'kscale', None) is None:
-            PACK_BATCH['items'].append(self)        # flushed as ONE launch by pack_batch_end()
-            return
-        check(_L.hnd_pack_weights(self.src.data_ptr(), self.buf.data_ptr(), *self.args, stream_ptr()),
-              'hnd_pack_weights')
-        if getattr(self, 'kscale', None) is not None:       # a per-channel scale of the K operand folded into the weights
-            check(_L.hnd_scale_packed_k(self.buf.data_ptr(), round_up(self.rows, 64), self.kdim, self.ni * self.nj,
-                                        self.chan_pad, self.kscale.data_ptr(), min(self.kscale.numel(), self.chan_pad),
-                                        stream_ptr()), 'hnd_scale_packed_k')
-        self.refresh_bx3()
+        self.fill()
+        self.refresh_images()
+
+    def refresh_images(self):
+        if self.bx3 is not None:
+            bx3_image(self.buf, self.rows_pad, self.kdim, self.groups, self.group_stride, out=self.bx3)
+        if self.bxs is not None:
+            bxs_image(self.buf, self.rows_pad, self.kdim, self.groups, self.group_stride, out=self.bxs)
 
     def can_bx3(self):
-        return self.ni * self.nj == 1 and self.kdim == self.chan_pad          # tap-free operands only
+        return (self.taps == 1 and self.kdim == self.chan_pad and self.rows_pad % 64 == 0          # tap-free operands only
+                and (self.kdim == 128 or (self.kdim % 256 == 0 and self.kdim <= 2048)))
 
     def can_bxs(self):
-        return self.kdim % 128 == 0 and self.chan_pad % 64 == 0 and self.kdim == self.ni * self.nj * self.chan_pad
+        return (self.groups == 1 and self.kdim % 128 == 0 and self.chan_pad % 64 == 0 and self.rows_pad % 64 == 0
+                and self.kdim == self.taps * self.chan_pad)
 
-    def refresh_bx3(self):
-        """the pre-split images of this operand: made with the first pack while the emulation is on (or by the first launch
-        that asks for one: attach_image), and from then on re-made only while a launch descriptor points at them (conv_desc
-        sets used3 / useds and brings a stale image up to date when it attaches one)"""
-        if self.can_bx3():
-            have = getattr(self, 'bx3', None) is not None
-            if (bx3_on() and not have) or (have and getattr(self, 'used3', None) is not False):
-                self.bx3 = bx3_image(self.buf, round_up(self.rows, 64), self.kdim, out=getattr(self, 'bx3', None), force=True)
-        if self.can_bxs():
-            have = getattr(self, 'bxs', None) is not None
-            if (bx3_on() and not have) or (have and getattr(self, 'useds', None) is not False):
-                self.bxs = bxs_image(self.buf, round_up(self.rows, 64), self.kdim, out=getattr(self, 'bxs', None), force=True)
+    def attach(self, which):
+        """the image ('bx3' / 'bxs') a launch descriptor is about to point at, made now if it is the first to ask;
+        None when the kernel cannot use this operand"""
+        if which == 'bx3':
+            if self.bx3 is None and self.can_bx3():
+                self.bx3 = bx3_image(self.buf, self.rows_pad, self.kdim, self.groups, self.group_stride)
+            return self.bx3
+        if self.bxs is None and self.can_bxs():
+            self.bxs = bxs_image(self.buf, self.rows_pad, self.kdim, self.groups, self.group_stride)
+        return self.bxs
 
-    def attach_image(self, which):
-        """a launch descriptor is about to point at the image: make it if there is none yet (`with ops.emulation('force')`
-        under HND_BF16X3=0), bring a stale one up to date, and from now on every re-pack re-makes it"""
-        if which == 3 and getattr(self, 'used3', None) is False and self.can_bx3():
-            self.used3 = True
-            self.bx3 = bx3_image(self.buf, round_up(self.rows, 64), self.kdim, out=getattr(self, 'bx3', None), force=True)
-        elif which == 's' and getattr(self, 'useds', None) is False and self.can_bxs():
-            self.useds = True
-            self.bxs = bxs_image(self.buf, round_up(self.rows, 64), self.kdim, out=getattr(self, 'bxs', None), force=True)
+
+class DirectWeights(PackedWeight):
+    """One conv weight packed for the direct launches (hnd_pack_weights).  w: torch OIHW parameter (device, contiguous);
+    taps = (i0, istep, ni, j0, jstep, nj) or None = all.  kscale: per-channel scale of the GEMM's K operand folded into
+    the packed weights (hnd_scale_packed_k)."""
+    def __init__(self, w, transposed=False, chan_pad=None, taps=None, kscale=None):
+        cout, cin, kh, kw = w.shape
+        assert w.is_contiguous() and w.dtype == torch.float32
+        if taps is None:
+            taps = (0, 1, kh, 0, 1, kw)
+        i0, istep, ni, j0, jstep, nj = taps
+        chans = cout if transposed else cin
+        rows = cin if transposed else cout
+        if chan_pad is None:
+            chan_pad = chan_pad_of(chans)
+        kdim = round_up(ni * nj * chan_pad, 32)
+        PackedWeight.__init__(self, torch.empty(round_up(rows, 64) * kdim, dtype=torch.float32, device=w.device), rows,
+                              kdim, chan_pad, chans, taps=ni * nj)
+        self.src, self.kscale = w, kscale
+        self.args = (cout, cin, kh, kw, int(transposed), chan_pad, i0, istep, ni, j0, jstep, nj)
+        self.repack()
+
+    def repack(self):
+        if PACK_BATCH['open'] and self.kscale is None:
+            PACK_BATCH['items'].append(self)        # flushed as ONE launch by pack_batch_end()
+        else:
+            PackedWeight.repack(self)
+
+    def fill(self):
+        check(_L.hnd_pack_weights(self.src.data_ptr(), self.buf.data_ptr(), *self.args, stream_ptr()), 'hnd_pack_weights')
+        if self.kscale is not None:         # a per-channel scale of the K operand folded into the weights
+            check(_L.hnd_scale_packed_k(self.buf.data_ptr(), self.rows_pad, self.kdim, self.taps, self.chan_pad,
+                                        self.kscale.data_ptr(), min(self.kscale.numel(), self.chan_pad), stream_ptr()),
+                  'hnd_scale_packed_k')
+
+
+pack_weights = DirectWeights
 
 
 # A caller that refreshes many small operands in a row (the trainable head after every optimizer step) brackets the loop
-# with pack_batch_begin() / pack_batch_end(): the repack() calls in between are collected into one batched launch.
+# with pack_batch_begin() / pack_batch_end(): the DirectWeights.repack() calls in between are collected into one batched
+# launch.
 PACK_BATCH = {'open': False, 'items': []}
 
 
@@ -184,30 +220,7 @@ def pack_batch_end():
         (d.cout, d.cin, d.kh, d.kw, d.transposed, d.chan_pad, d.i0, d.istep, d.ni, d.j0, d.jstep, d.nj) = pw.args
     check(_L.hnd_pack_weights_batched(arr, len(items), stream_ptr()), 'hnd_pack_weights_batched')
     for pw in items:
-        pw.refresh_bx3()
-
-
-def pack_weights(w, transposed=False, chan_pad=None, taps=None, kscale=None):
-    """w: torch OIHW parameter (device, contiguous).  taps = (i0, istep, ni, j0, jstep, nj) or None = all.
-    kscale: per-channel scale of the GEMM's K operand folded into the packed weights (hnd_scale_packed_k)."""
-    cout, cin, kh, kw = w.shape
-    assert w.is_contiguous() and w.dtype == torch.float32
-    if taps is None:
-        taps = (0, 1, kh, 0, 1, kw)
-    i0, istep, ni, j0, jstep, nj = taps
-    chans = cout if transposed else cin
-    rows = cin if transposed else cout
-    if chan_pad is None:
-        chan_pad = chan_pad_of(chans)
-    pw = PackedWeight()
-    pw.rows, pw.ni, pw.nj, pw.chan_pad, pw.chan_real, pw.src = rows, ni, nj, chan_pad, chans, w
-    pw.kdim = round_up(ni * nj * chan_pad, 32)
-    pw.buf = torch.empty(round_up(rows, 64) * pw.kdim, dtype=torch.float32, device=w.device)
-    pw.args = (cout, cin, kh, kw, int(transposed), chan_pad, i0, istep, ni, j0, jstep, nj)
-    pw.kscale = kscale
-    pw.used3 = pw.useds = False
-    pw.repack()
-    return pw
+        pw.refresh_images()
 
 
 def fbn_fold(weight, bias, mean, var, eps=0.0, cs=None, out=None):
@@ -238,7 +251,7 @@ class ConvLaunch(object):
         self.refresh_variant()
 
     def refresh_variant(self):
-        """call again after editing the descriptor (grouped weights): the dispatch may change"""
+        """call again after editing the descriptor or the picker's environment: the dispatch may change"""
         need = int(_L.hnd_conv2d_igemm_workspace(self.ref))
         if need == 0:
             self.relay, self.desc.relay_ws = None, None
@@ -266,16 +279,19 @@ def _nhwc(t):
 def conv_desc(x, pw, y, *, kh, kw, oh, ow, sh, dh, bh, sw, dw, bw, cout, y_sh=1, y_oh=0, y_sw=1, y_ow=0,
               pro_scale=None, pro_shift=None, pro_relu=False, epi_scale=None, epi_shift=None, res1=None,
               res1_up=False, res2=None, mask=None, relu=False, stats=None, mask_bits=None, mask_out=None,
-              bwd_stats=None, rows_per_image=None):
+              bwd_stats=None, rows_per_image=None, w_group_rows=0):
     """Generic descriptor (see include/hnd_hip.h).  x, y, res*, mask are NHWC tensors; mask_bits / mask_out are uint8
     ReLU-mask nibble tensors of y's geometry with a quarter of its channels (mask_nibbles_like).
     bwd_stats = (x_raw, scale, shift, mean, rstd, relu): `stats` receives the BatchNorm-backward partials of the stored
     y (hnd_conv_desc.bwd_x) instead of its sum / sum of squares.
     rows_per_image: GEMM rows ONE image contributes (default oh * ow; the Winograd launches fold the batch into ow and say
-    components x tiles per image): what hnd_bf16x3_recommended prices the emulation kernel on -- never the batch."""
+    components x tiles per image): what hnd_bf16x3_recommended prices the emulation kernel on -- never the batch.
+    w_group_rows: GEMM rows that each of the pw.groups weight matrices of a grouped operand multiplies (the Winograd
+    component GEMMs: tiles per component)."""
     n, h, w, cin = _nhwc(x)
     ny, yh, yw, ldc = _nhwc(y)
     assert ny == n and pw.kdim >= kh * kw * cin and pw.chan_pad == cin, (pw.kdim, kh, kw, cin, pw.chan_pad)
+    assert (pw.groups > 1) == (w_group_rows > 0), (pw.groups, w_group_rows)
     if pro_scale is not None and pro_shift is None:
         pro_shift = _zeros(cin, x.device)
     d = ConvDesc()
@@ -289,6 +305,7 @@ def conv_desc(x, pw, y, *, kh, kw, oh, ow, sh, dh, bh, sw, dw, bw, cout, y_sh=1,
     d.kh, d.kw = kh, kw
     d.sh, d.dh, d.bh, d.sw, d.dw, d.bw = sh, dh, bh, sw, dw, bw
     d.kdim = pw.kdim
+    d.w_group_rows, d.w_group_stride = w_group_rows, pw.group_stride
     d.pro_relu, d.relu = int(pro_relu), int(relu)
     if res1 is not None and res1_up:
         d.res1_mode, d.res1_h, d.res1_w = 1, res1.shape[1], res1.shape[2]
@@ -303,16 +320,12 @@ def conv_desc(x, pw, y, *, kh, kw, oh, ow, sh, dh, bh, sw, dw, bw, cout, y_sh=1,
     assert mask is None or mask_bits is None
     d.mask_bits, d.mask_out = ptr(mask_bits), ptr(mask_out)
     # fp32 emulated on the bf16 matrix pipe: by layer, never by batch
-    rpi = oh * ow if rows_per_image is None else rows_per_image
-    want = BX3_MODE[0] == 'force' or (BX3_MODE[0] == 'policy' and bx3_recommended(rpi, pw.kdim, cout))
-    if want and getattr(pw, 'used3', None) is False:
-        pw.attach_image(3)
-    d.w_bf16x3 = ptr(getattr(pw, 'bx3', None) if want else None)
+    rpi, mode = oh * ow if rows_per_image is None else rows_per_image, BX3_MODE[0]
+    if mode in ('force', 'bx3') or (mode == 'policy' and bx3_recommended(rpi, pw.kdim, cout)):
+        d.w_bf16x3 = ptr(pw.attach('bx3'))
     # ... and its B-streamed build for what the B-resident kernel does not take (taps, long K, strided outputs, statistics)
-    want = BX3_MODE[0] == 'force' or (BX3_MODE[0] == 'policy' and bxs_recommended(rpi, pw.kdim, cout, kh * kw))
-    if want and getattr(pw, 'useds', None) is False:
-        pw.attach_image('s')
-    d.w_bf16x3s = ptr(getattr(pw, 'bxs', None) if want else None)
+    if mode in ('force', 'bxs') or (mode == 'policy' and bxs_recommended(rpi, pw.kdim, cout, kh * kw)):
+        d.w_bf16x3s = ptr(pw.attach('bxs'))
     if stats is not None:
         assert stats.numel() >= stats_tiles(n * oh * ow) * 2 * cout
     if bwd_stats is not None:
@@ -323,7 +336,7 @@ def conv_desc(x, pw, y, *, kh, kw, oh, ow, sh, dh, bh, sw, dw, bw, cout, y_sh=1,
         d.bwd_x, d.bwd_scale, d.bwd_shift, d.bwd_mean, d.bwd_rstd = ptr(bx), ptr(bsc), ptr(bsh), ptr(bmu), ptr(brs)
         d.bwd_relu = int(brelu)
     keep = (x, pw, y, pro_scale, pro_shift, epi_scale, epi_shift, res1, res2, mask, stats, mask_bits, mask_out,
-            bwd_stats, getattr(pw, 'bx3', None), getattr(pw, 'bxs', None))
+            bwd_stats)                  # (pw holds its images: once made they live as long as it does)
     return ConvLaunch(d, keep, flops=2 * n * oh * ow * min(cout, pw.rows) * kh * kw * min(cin, pw.chan_real))
 
 
@@ -687,26 +700,44 @@ def wino_tiles_pad(n, h, w, tile=2):
     return int(_L.hnd_wino_tiles_pad(n, h, w, tile))
 
 
-class WinoWeights(object):
-    """U = G g G^T of one 3x3 conv weight in packed GEMM-operand layout [(tile+2)^2][rows_pad][depth]; dgrad:
-    transposed conv.  tile = 2 (F(2x2,3x3)), 4 (F(4x4,3x3)) or 6 (F(6x6,3x3))."""
-
-    def __init__(self, weight, dgrad=False, tile=2):
+class _WinogradWeights(PackedWeight):
+    """One k x k conv weight in the Winograd domain: a grouped operand of ncomp = (tile+k-1)^2 GEMM matrices
+    [rows_pad][depth], one per component; dgrad: of the transposed conv.  The subclasses name k, the tiles and the
+    kernel that fills the buffer."""
+    def __init__(self, weight, dgrad, tile):
         cout, cin, kh, kw = weight.shape
-        assert kh == 3 and kw == 3 and weight.is_contiguous() and tile in (2, 4, 6)
-        self.src, self.dgrad, self.tile, self.ncomp = weight, dgrad, tile, (tile + 2) ** 2
-        self.rows, self.depth = (cin, cout) if dgrad else (cout, cin)
-        assert self.depth % 32 == 0, 'Winograd path needs a GEMM depth that is a multiple of 32'
-        self.rows_pad = round_up(self.rows, 64)
-        self.buf = torch.empty(self.ncomp * self.rows_pad * self.depth, dtype=torch.float32, device=weight.device)
-        self.bx3 = None
+        assert kh == self.K and kw == self.K and weight.is_contiguous() and tile in self.TILES
+        rows, depth = (cin, cout) if dgrad else (cout, cin)
+        assert depth % 32 == 0, 'Winograd path needs a GEMM depth that is a multiple of 32'
+        ncomp, rows_pad = (tile + self.K - 1) ** 2, round_up(rows, 64)
+        PackedWeight.__init__(self, torch.empty(ncomp * rows_pad * depth, dtype=torch.float32, device=weight.device),
+                              rows, depth, depth, groups=ncomp, group_stride=rows_pad * depth)
+        self.src, self.dgrad, self.tile, self.ncomp, self.depth = weight, dgrad, tile, ncomp, depth
         self.repack()
 
-    def repack(self):
-        cout, cin = self.src.shape[0], self.src.shape[1]
-        check(_L.hnd_wino_weights(ptr(self.src), ptr(self.buf), cout, cin, int(self.dgrad), self.tile, stream_ptr()),
-              'hnd_wino_weights')
-        self.bx3 = bx3_image(self.buf, self.rows_pad, self.depth, self.ncomp, self.rows_pad * self.depth, out=self.bx3)
+    def fill(self):
+        check(getattr(_L, self.KERNEL)(ptr(self.src), ptr(self.buf), self.src.shape[0], self.src.shape[1],
+                                       int(self.dgrad), self.tile, stream_ptr()), self.KERNEL)
+
+
+class WinoWeights(_WinogradWeights):
+    """U = G g G^T of one 3x3 conv weight, [(tile+2)^2][rows_pad][depth]; tile = 2 (F(2x2,3x3)), 4 (F(4x4,3x3)) or 6
+    (F(6x6,3x3))."""
+    K, TILES, KERNEL = 3, (2, 4, 6), 'hnd_wino_weights'
+
+    def __init__(self, weight, dgrad=False, tile=2):
+        _WinogradWeights.__init__(self, weight, dgrad, tile)
+
+
+def _component_gemms(v, ww, m, cout, tiles_pad, n, oh, ow):
+    """the ww.ncomp component GEMMs V -> M of a Winograd launch with oh x ow outputs per image, as ONE grouped igemm
+    launch (tiles_pad rows per component)"""
+    tiles = ((oh + ww.tile - 1) // ww.tile) * ((ow + ww.tile - 1) // ww.tile)        # per image
+    gemm = conv_desc(v, ww, m, kh=1, kw=1, oh=1, ow=ww.ncomp * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0, cout=cout,
+                     rows_per_image=ww.ncomp * tiles, w_group_rows=tiles_pad)
+    gemm.flops = 2 * ww.ncomp * n * tiles * ww.rows * ww.depth                   # multiplies actually executed
+    gemm.alg_flops = 2 * n * oh * ow * ww.rows * ww.K ** 2 * ww.depth            # the direct convolution it computes
+    return gemm
 
 
 class WinoConv(object):
@@ -738,20 +769,8 @@ class WinoConv(object):
             assert t is None or tuple(t.shape) == tuple(y.shape)
         self.v = v[:need_v].view(1, 1, nc * self.tiles_pad, c)
         self.m = m[:need_m].view(1, 1, nc * self.tiles_pad, self.cout)
-        pw = PackedWeight.__new__(PackedWeight)
-        pw.buf, pw.kdim, pw.rows, pw.chan_pad, pw.chan_real = ww.buf, ww.depth, ww.rows, c, c
-        pw.bx3 = ww.bx3
-        self.gemm = conv_desc(self.v, pw, self.m, kh=1, kw=1, oh=1, ow=nc * self.tiles_pad, sh=1, dh=1, bh=0, sw=1,
-                              dw=1, bw=0, cout=self.cout,
-                              rows_per_image=nc * ((h + tile - 1) // tile) * ((w + tile - 1) // tile))
-        self.gemm.desc.w_group_rows = self.tiles_pad
-        self.gemm.desc.w_group_stride = ww.rows_pad * ww.depth
-        self.gemm.refresh_variant()
-        tiles = n * ((h + tile - 1) // tile) * ((w + tile - 1) // tile)
-        self.gemm.flops = 2 * nc * tiles * ww.rows * ww.depth          # multiplies actually executed
-        self.gemm.alg_flops = 2 * n * h * w * ww.rows * 9 * ww.depth   # the direct 3x3 convolution it computes
-        self.flops = self.gemm.flops
-        self.variant = self.gemm.variant
+        self.gemm = _component_gemms(self.v, ww, self.m, self.cout, self.tiles_pad, n, h, w)
+        self.flops, self.variant = self.gemm.flops, self.gemm.variant
 
     @staticmethod
     def scratch_elems(n, h, w, cin, cout, tile=2):
@@ -789,27 +808,12 @@ class WinoConv(object):
         self._run_output(stream)
 
 
-class Wino2Weights(object):
-    """F(tile x tile, 2x2) weights (tile 4 or 6) of one 2x2 conv in packed GEMM-operand layout
-    [(tile+1)^2][rows_pad][depth]; dgrad: transposed conv."""
+class Wino2Weights(_WinogradWeights):
+    """F(tile x tile, 2x2) weights (tile 4 or 6) of one 2x2 conv, [(tile+1)^2][rows_pad][depth]."""
+    K, TILES, KERNEL = 2, (4, 6), 'hnd_wino2_weights'
 
     def __init__(self, weight, dgrad=False, tile=4):
-        cout, cin, kh, kw = weight.shape
-        assert kh == 2 and kw == 2 and weight.is_contiguous() and tile in (4, 6)
-        self.src, self.dgrad, self.tile, self.ncomp = weight, dgrad, tile, (tile + 1) ** 2
-        self.rows, self.depth = (cin, cout) if dgrad else (cout, cin)
-        assert self.depth % 32 == 0, 'Winograd path needs a GEMM depth that is a multiple of 32'
-        self.rows_pad = round_up(self.rows, 64)
-        self.buf = torch.empty(self.ncomp * self.rows_pad * self.depth, dtype=torch.float32, device=weight.device)
-        self.bx3 = None
-        self.repack()
-
-    def repack(self):
-        cout, cin = self.src.shape[0], self.src.shape[1]
-        check(_L.hnd_wino2_weights(self.src.data_ptr(), ptr(self.buf), cout, cin, int(self.dgrad), self.tile,
-                                   stream_ptr()),
-              'hnd_wino2_weights')
-        self.bx3 = bx3_image(self.buf, self.rows_pad, self.depth, self.ncomp, self.rows_pad * self.depth, out=self.bx3)
+        _WinogradWeights.__init__(self, weight, dgrad, tile)
 
 
 class Wino2Conv(object):
@@ -847,18 +851,7 @@ class Wino2Conv(object):
             assert bwd_stats[6].numel() >= self.stats_blocks(n, oh, ow, self.cout, 6) * 2 * self.cout
         self.v = v[:need_v].view(1, 1, nc * self.tiles_pad, c)
         self.m = m[:need_m].view(1, 1, nc * self.tiles_pad, self.cout)
-        pw = PackedWeight.__new__(PackedWeight)
-        pw.buf, pw.kdim, pw.rows, pw.chan_pad, pw.chan_real = ww.buf, ww.depth, ww.rows, c, c
-        pw.bx3 = ww.bx3
-        self.gemm = conv_desc(self.v, pw, self.m, kh=1, kw=1, oh=1, ow=nc * self.tiles_pad, sh=1, dh=1, bh=0, sw=1,
-                              dw=1, bw=0, cout=self.cout,
-                              rows_per_image=nc * ((oh + self.tile - 1) // self.tile) * ((ow + self.tile - 1) // self.tile))
-        self.gemm.desc.w_group_rows = self.tiles_pad
-        self.gemm.desc.w_group_stride = ww.rows_pad * ww.depth
-        self.gemm.refresh_variant()
-        tiles = n * ((oh + self.tile - 1) // self.tile) * ((ow + self.tile - 1) // self.tile)
-        self.gemm.flops = 2 * nc * tiles * ww.rows * ww.depth
-        self.gemm.alg_flops = 2 * n * oh * ow * ww.rows * 4 * ww.depth  # the direct 2x2 convolution it computes
+        self.gemm = _component_gemms(self.v, ww, self.m, self.cout, self.tiles_pad, n, oh, ow)
         self.flops, self.variant = self.gemm.flops, self.gemm.variant
 
     @staticmethod

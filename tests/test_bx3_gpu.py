@@ -66,12 +66,10 @@ def test_bx3_1x1_conv_against_fp64_beside_the_native_kernel(ops, cin, cout, n, h
         l0 = ops.conv_forward(xd, pk, y0, 1, stride, 0, **kw)
     assert not l0.variant.startswith('bx3')
     l0.run()
-    pk.bx3 = ops.bx3_image(pk.buf, ops.round_up(cout, 64), cin, force=True)
-    assert pk.bx3 is not None
     y1 = torch.full_like(y0, float('nan'))
     with ops.emulation('force'):
         l1 = ops.conv_forward(xd, pk, y1, 1, stride, 0, **kw)
-    assert l1.variant == 'bx3_64', l1.variant
+    assert l1.variant == 'bx3_64' and pk.bx3 is not None, l1.variant
     l1.run()
     ops.sync_check()
     want = ref.permute(0, 2, 3, 1)
@@ -103,8 +101,6 @@ def test_bx3_bottleneck_conv3_with_residual_relu_and_mask_nibbles(ops, cin, cout
     xd, rd, pk = _nhwc(x), _nhwc(res), ops.pack_weights(wt.to(DEV).contiguous())
     outs = {}
     for emu in (False, True):
-        if emu:
-            pk.bx3 = ops.bx3_image(pk.buf, cout, cin, force=True)
         y = torch.full((n, h, w, cout), float('nan'), device=DEV)
         bits = torch.full((n, h, w, cout // 4), 255, dtype=torch.uint8, device=DEV)
         with ops.emulation('force' if emu else 'off'):
@@ -143,8 +139,6 @@ def test_bx3_masked_data_gradient_with_residual(ops, cin, cout, n, h, w):
             | ((av[..., 3] > 0).to(torch.uint8) << 3)).contiguous()
     errs = {}
     for emu in (False, True):
-        if emu:
-            pk.bx3 = ops.bx3_image(pk.buf, cout, cin, force=True)
         y = torch.full((n, h, w, cout), float('nan'), device=DEV)
         with ops.emulation('force' if emu else 'off'):
             l = ops.conv_forward(xd, pk, y, 1, 1, 0, res1=rd, mask_bits=bits)
@@ -179,7 +173,6 @@ def test_bx3_conv3_data_gradient_masked_by_nibbles_made_from_the_activation(ops,
     with ops.emulation('off'):
         l0 = ops.conv_forward(xd, pk, y0, 1, 1, 0, mask=ad)
     l0.run()
-    pk.bx3 = ops.bx3_image(pk.buf, cout, cin, force=True)
     y1 = torch.full_like(y0, float('nan'))
     with ops.emulation('force'):
         l1 = ops.conv_forward(xd, pk, y1, 1, 1, 0, mask_bits=bits)
@@ -233,8 +226,6 @@ def test_bx3_randomised_shapes_and_epilogues_against_the_native_kernel(ops):
         pk = ops.pack_weights(wt)
         outs = []
         for emu in (False, True, True):
-            if emu and getattr(pk, 'bx3', None) is None:
-                pk.bx3 = ops.bx3_image(pk.buf, ops.round_up(cout, 64), cin, force=True)
             y = torch.full((n, oh, ow, cout), float('nan'), device=DEV)
             mo = torch.full((n, oh, ow, cout // 4), 255, dtype=torch.uint8, device=DEV) if mask_out else None
             with ops.emulation('force' if emu else 'off'):
@@ -272,8 +263,6 @@ def test_bx3_fpn_lateral_with_the_upsampled_top_down_map(ops):
     xd, td, pk = _nhwc(x), _nhwc(top), ops.pack_weights(wt.to(DEV).contiguous())
     errs = {}
     for emu in (False, True):
-        if emu:
-            pk.bx3 = ops.bx3_image(pk.buf, cout, cin, force=True)
         y = torch.full((n, h, w, cout), float('nan'), device=DEV)
         with ops.emulation('force' if emu else 'off'):
             l = ops.conv_forward(xd, pk, y, 1, 1, 0, epi_shift=bias.to(DEV), res1=td, res1_up=True)
@@ -298,10 +287,7 @@ def test_bx3_winograd_component_gemms_match_the_native_path(ops, c, n, h, w):
     xd, wd = _nhwc(x), wt.to(DEV).contiguous()
     outs = {}
     for emu in (False, True):
-        with ops.emulation('off'):
-            ww = ops.WinoWeights(wd, False, 6)
-        if emu:
-            ww.bx3 = ops.bx3_image(ww.buf, ww.rows_pad, ww.depth, ww.ncomp, ww.rows_pad * ww.depth, force=True)
+        ww = ops.WinoWeights(wd, False, 6)
         nv, nm = ops.WinoConv.scratch_elems(n, h, w, c, c, 6)
         v, m = torch.empty(nv, device=DEV), torch.empty(nm, device=DEV)
         y = torch.full((n, h, w, c), float('nan'), device=DEV)
@@ -324,7 +310,7 @@ LAYERS = [   # (cin, cout, h, w, stride): 1x1 launches of the frozen layers and 
 ]
 
 
-def test_bx3_choice_depends_on_the_layer_and_never_on_the_batch(ops):
+def test_bx3_choice_and_image_depend_on_the_layer_and_never_on_the_batch(ops):
     """whether a launch runs on the emulation is decided by hnd_bf16x3_recommended from the rows ONE
     image contributes, the depth and the output channels; the batch of the launch changes nothing -- also for row counts
     that are no multiple of 64 or of 4 (25 x 42 = 1050 rows per image) and for fewer chunks than teams (batch 1)."""
@@ -332,7 +318,7 @@ def test_bx3_choice_depends_on_the_layer_and_never_on_the_batch(ops):
     for cin, cout, h, w, stride in LAYERS:
         wt = torch.randn(cout, cin, 1, 1).to(DEV) / cin ** 0.5
         pk = ops.pack_weights(wt)
-        assert ops.bx3_on() and pk.bx3 is not None          # the default build attaches an image to every tap-free operand
+        assert ops.bx3_on() and pk.bx3 is None and pk.bxs is None       # no image before a launch asks for one
         oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
         variants = set()
         for n in (1, 2, 3, 16):
@@ -342,6 +328,7 @@ def test_bx3_choice_depends_on_the_layer_and_never_on_the_batch(ops):
         assert len(variants) == 1, (cin, cout, h, w, variants)
         assert variants.pop() == ops.bx3_recommended(oh * ow, cin, cout)
         picked.append(ops.bx3_recommended(oh * ow, cin, cout))
+        assert (pk.bx3 is not None) == picked[-1], (cin, cout, h, w)          # an image only where the policy picked it
     assert any(picked) and not all(picked), picked
     # Winograd component GEMMs fold the batch into their row count: the launch states rows per image itself
     wd = (torch.randn(256, 256, 3, 3) / 48).to(DEV)
@@ -352,7 +339,7 @@ def test_bx3_choice_depends_on_the_layer_and_never_on_the_batch(ops):
         conv = ops.WinoConv(torch.empty(n, 50, 84, 256, device=DEV), ww, torch.empty(n, 50, 84, 256, device=DEV),
                             torch.empty(nv, device=DEV), torch.empty(nm, device=DEV))
         vs.add(conv.gemm.variant)
-    assert vs == {'bx3_64'}, vs
+    assert vs == {'bx3_64'} and ww.bx3 is not None and ww.bxs is None, vs
 
 
 @pytest.mark.parametrize('cin,cout,h,w,stride,epi', [
@@ -406,10 +393,11 @@ def _rowsum_abs(x, wt):
     return x.abs().double().flatten(0, 2) @ wt.abs().double().flatten(1).t()
 
 
-def test_weight_images_follow_the_weights_once_a_launch_points_at_them(ops):
-    """A re-packed operand re-makes its pre-split images only while a launch descriptor reads them: an image nobody reads may go stale,
-    attaching it brings it up to date, and from then on every re-pack refreshes it -- the launch always computes with the
-    CURRENT weights, bit for bit what a freshly packed operand gives."""
+def test_weight_images_are_made_by_the_first_launch_and_follow_every_repack(ops):
+    """A packed operand has no pre-split image until a launch descriptor asks for one (a re-pack makes none); attaching makes
+    it from the CURRENT weights, and from then on every re-pack refreshes it in place -- also one made while the emulation
+    is off -- so the launch always computes with the current weights, bit for bit what a freshly packed operand gives.
+    The Winograd operands (grouped: one matrix per component GEMM) follow the same rule."""
     g = torch.Generator().manual_seed(5)
     for k, cin, cout, h, w, pad in ((1, 256, 128, 40, 64, 0), (2, 64, 128, 41, 65, 1)):
         x = torch.randn(2, h, w, cin, generator=g).to(DEV)
@@ -425,25 +413,60 @@ def test_weight_images_follow_the_weights_once_a_launch_points_at_them(ops):
             return launch.variant, y_ref.clone()
 
         pk = ops.pack_weights(wt)
-        img = pk.bx3 if k == 1 else pk.bxs
-        assert img is not None and pk.used3 is False and pk.useds is False
-        before = img.clone()
+        assert pk.bx3 is None and pk.bxs is None                # no launch has asked: no image
         wt.mul_(1.5).add_(0.01)                                 # an optimizer step
         pk.repack()
-        assert torch.equal(img, before)                         # nobody reads it: not re-made
+        assert pk.bx3 is None and pk.bxs is None                # a re-pack makes none
         with ops.emulation('force'):
-            launch = ops.conv_forward(x, pk, y, k, 1, pad)      # attaching brings it up to date
-        assert (pk.used3 if k == 1 else pk.useds) is True and not torch.equal(img, before)
+            launch = ops.conv_forward(x, pk, y, k, 1, pad)      # attaching makes it from the current weights
+        img = pk.bx3 if k == 1 else pk.bxs
+        assert img is not None
         launch.run()
         ops.sync_check()
         variant, want = fresh()
         assert launch.variant == variant and variant.startswith('bx3' if k == 1 else 'bxs'), (launch.variant, variant)
         assert torch.equal(y, want)
         wt.mul_(0.5).sub_(0.02)                                 # the next step: the re-pack refreshes the image itself
-        pk.repack()
+        with ops.emulation('off'):
+            pk.repack()
+        assert (pk.bx3 if k == 1 else pk.bxs) is img
         launch.run()
         ops.sync_check()
         assert torch.equal(y, fresh()[1])
+    # F(6x6,3x3) and F(6x6,2x2) weights, 256 deep: the launch built under 'force', the weights changed, the re-pack made
+    # while the emulation is off -- the launch must not go on with the old image
+    c, n, h, w = 256, 2, 30, 42
+    x = torch.randn(n, h, w, c, generator=g).to(DEV)
+    for make, k in ((ops.WinoWeights, 3), (ops.Wino2Weights, 2)):
+        wt = (torch.randn(c, c, k, k, generator=g) / (c * k * k) ** 0.5).to(DEV)
+
+        oh, ow = (h, w) if k == 3 else (h + 1, w + 1)          # (the 2x2 conv with padding 1)
+
+        def build(ww, out):
+            if k == 3:
+                nv, nm = ops.WinoConv.scratch_elems(n, h, w, c, c, 6)
+                return ops.WinoConv(x, ww, out, torch.empty(nv, device=DEV), torch.empty(nm, device=DEV))
+            nv, nm = ops.Wino2Conv.scratch_elems(n, oh, ow, c, c, 6)
+            return ops.Wino2Conv(x, ww, out, torch.empty(nv, device=DEV), torch.empty(nm, device=DEV), 1)
+
+        ww = make(wt, False, 6)
+        assert ww.bx3 is None and ww.bxs is None
+        y, y_ref = torch.empty(n, oh, ow, c, device=DEV), torch.empty(n, oh, ow, c, device=DEV)
+        with ops.emulation('force'):
+            conv = build(ww, y)
+        img = ww.bx3
+        assert conv.gemm.variant == 'bx3_64' and img is not None and ww.bxs is None, conv.gemm.variant
+        wt.mul_(1.5).add_(0.01)
+        with ops.emulation('off'):
+            ww.repack()
+        assert ww.bx3 is img
+        conv.run()
+        with ops.emulation('force'):
+            ref = build(make(wt, False, 6), y_ref)
+        assert ref.gemm.variant == conv.gemm.variant
+        ref.run()
+        ops.sync_check()
+        assert not bool(torch.isnan(y).any()) and torch.equal(y, y_ref), make.__name__
 
 
 def test_bx3_non_finite_inputs_are_loud_and_denormals_behave_as_documented(ops):

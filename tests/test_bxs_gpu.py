@@ -34,10 +34,11 @@ def _rel(a, ref):
 
 
 def _pair(ops, build):
-    """build(): a launch made under the current emulation mode -> (native launch, emulated launch)"""
+    """build(): a launch made under the current emulation mode -> (native launch, B-streamed emulated launch: no bx3
+    image attached, so tap-free shapes the B-resident kernel would take first come here too)"""
     with ops.emulation('off'):
         l0 = build()
-    with ops.emulation('force'):
+    with ops.emulation('bxs'):
         l1 = build()
     assert not l0.variant.startswith('bx'), l0.variant
     assert l1.variant.startswith('bxs'), l1.variant
@@ -49,11 +50,22 @@ def _pair(ops, build):
     (256, 256, 4, 50, 84, 3, 2, 1),          # layer3.0.conv2
     (512, 512, 8, 25, 42, 3, 2, 1),          # layer4.0.conv2: 13 x 21 outputs, tiles fewer than workgroups x 2
     (128, 64, 3, 37, 53, 3, 1, 1),           # 256 x 64 tile, rows with a tail
-    (2048, 512, 16, 25, 42, 1, 1, 0),        # layer4.x.conv1: long K, no taps
-    (1024, 2048, 4, 50, 84, 1, 2, 0),        # layer4.0.downsample: stride 2
     (64, 128, 2, 61, 77, 2, 1, 1),           # a head conv: two taps per 128-k iteration
 ])
 def test_bxs_conv_against_fp64_beside_the_native_kernel(ops, cin, cout, n, h, w, k, stride, pad):
+    _bxs_conv_against_fp64(ops, cin, cout, n, h, w, k, stride, pad)
+
+
+@pytest.mark.parametrize('cin,cout,n,h,w,k,stride,pad', [
+    (2048, 512, 16, 25, 42, 1, 1, 0),        # layer4.x.conv1: long K, no taps
+    (1024, 2048, 4, 50, 84, 1, 2, 0),        # layer4.0.downsample: stride 2
+])
+def test_bxs_tap_free_conv_without_a_bx3_image_against_fp64(ops, cin, cout, n, h, w, k, stride, pad):
+    """tap-free shapes the B-resident kernel would take first: ops.emulation('bxs') attaches no bx3 image"""
+    _bxs_conv_against_fp64(ops, cin, cout, n, h, w, k, stride, pad)
+
+
+def _bxs_conv_against_fp64(ops, cin, cout, n, h, w, k, stride, pad):
     g = torch.Generator().manual_seed(3 + cin + cout + k)
     x = torch.randn(n, cin, h, w, generator=g) * torch.exp2(torch.randn(n, 1, h, w, generator=g) * 2)
     wt = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
@@ -61,7 +73,6 @@ def test_bxs_conv_against_fp64_beside_the_native_kernel(ops, cin, cout, n, h, w,
     ref = F.relu(F.conv2d(x.double(), wt.double(), None, stride, pad) * es.double()[None, :, None, None]
                  + eb.double()[None, :, None, None]).permute(0, 2, 3, 1)
     xd, pk = _nhwc(x), ops.pack_weights(wt.to(DEV).contiguous())
-    pk.bx3 = pk.used3 = None                      # (tap-free shapes the B-resident kernel would take first: no image, none made)
     oh, ow = ref.shape[1], ref.shape[2]
     ys = [torch.full((n, oh, ow, cout), float('nan'), device=DEV) for _ in range(4)]
     kw = dict(epi_scale=es.to(DEV), epi_shift=eb.to(DEV), relu=True)
@@ -69,7 +80,7 @@ def test_bxs_conv_against_fp64_beside_the_native_kernel(ops, cin, cout, n, h, w,
     l0, l1 = _pair(ops, lambda: ops.conv_forward(xd, pk, next(it), k, stride, pad, **kw))
     l0.run()
     l1.run()
-    with ops.emulation('force'):
+    with ops.emulation('bxs'):
         l2 = ops.conv_forward(xd, pk, ys[2], k, stride, pad, **kw)
         l3 = ops.conv_forward(xd, pk, ys[3], k, stride, pad, **kw)
     l2.run()
@@ -177,8 +188,8 @@ def test_bxs_stride2_data_gradients_parity_launches_with_masks(ops, cin, cout, n
                     'rel-L2 vs fp64 %.2e (native %.2e)' % (k, k, stride, cin, cout, len(ls), e1, e0))
 
 
-def test_bxs_randomised_shapes_against_the_native_kernel(ops):
-    """seeded sweep: taps 1x1 / 2x2 / 3x3, stride 1 / 2, K = 128 ... 4608, 64 ... 512 columns, row counts with tails and
+def test_bxs_randomised_shapes_without_bx3_images_against_the_native_kernel(ops):
+    """ops.emulation('bxs'), so tap-free shapes come here too rather than to the B-resident kernel.  Seeded sweep: taps 1x1 / 2x2 / 3x3, stride 1 / 2, K = 128 ... 4608, 64 ... 512 columns, row counts with tails and
     fewer tiles than workgroups, every epilogue operand -- each beside the native kernel (every element within 3e-5 of the
     result's rms), twice for reproducible bits.  A wrong hand-counted wait shows as garbage, not as a small error."""
     import random
@@ -211,11 +222,10 @@ def test_bxs_randomised_shapes_against_the_native_kernel(ops):
         if mask_bits:
             kw['mask_bits'] = torch.randint(0, 16, (n, oh, ow, cout // 4), generator=g, dtype=torch.uint8).to(DEV)
         pk = ops.pack_weights(wt)
-        pk.bx3 = pk.used3 = None
         outs = []
         for emu in (False, True, True):
             y = torch.full((n, oh, ow, cout), float('nan'), device=DEV)
-            with ops.emulation('force' if emu else 'off'):
+            with ops.emulation('bxs' if emu else 'off'):
                 l = ops.conv_forward(x, pk, y, k, stride, pad, **kw)
             assert l.variant.startswith('bxs') == emu, (case, k, cin, cout, l.variant)
             l.run()

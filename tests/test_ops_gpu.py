@@ -1184,9 +1184,8 @@ def test_bres_kernel_is_bit_identical_to_the_tiled_kernel(ops, case, monkeypatch
         y = torch.empty(1, 1, groups * tiles_pad, cout, device=DEV)
         ws = [torch.randn(cout, cin, 1, 1, generator=g).to(DEV) / cin ** 0.5 for _ in range(groups)]
         pks = [ops.pack_weights(wt) for wt in ws]
-        pk = ops.PackedWeight.__new__(ops.PackedWeight)
-        pk.buf = torch.cat([p.buf for p in pks])
-        pk.kdim, pk.rows, pk.chan_pad, pk.chan_real = pks[0].kdim, cout, cin, cin
+        pk = ops.PackedWeight(torch.cat([p.buf for p in pks]), cout, pks[0].kdim, cin, groups=groups,
+                              group_stride=pks[0].buf.numel())
     else:
         x = torch.randn(n, h, w, cin, generator=g).to(DEV)
         oh, ow = ops.conv_out_size(h, 1, s, 0), ops.conv_out_size(w, 1, s, 0)
@@ -1209,8 +1208,7 @@ def test_bres_kernel_is_bit_identical_to_the_tiled_kernel(ops, case, monkeypatch
         monkeypatch.setenv('HND_BRES2', '1' if mode == 'one_wave' else '0')
         if groups > 1:
             l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
-                              cout=cout)
-            l.desc.w_group_rows, l.desc.w_group_stride = tiles_pad, pks[0].buf.numel()
+                              cout=cout, w_group_rows=tiles_pad)
         else:
             l = ops.conv_forward(x, pk, y, 1, s, 0, epi_scale=sc, epi_shift=sh, res1=r, res1_up=res == 'up', mask=mk,
                                  relu=not msk, pro_scale=ps, pro_shift=pb, pro_relu=pro)
@@ -1278,9 +1276,8 @@ def test_bstream_kernel_is_bit_identical_to_the_tiled_kernel(ops, case, monkeypa
         y = torch.empty(1, 1, groups * tiles_pad, cout, device=DEV)
         ws = [torch.randn(cout, cin, 1, 1, generator=g).to(DEV) / cin ** 0.5 for _ in range(groups)]
         pks = [ops.pack_weights(wt) for wt in ws]
-        pk = ops.PackedWeight.__new__(ops.PackedWeight)
-        pk.buf = torch.cat([q.buf for q in pks])
-        pk.kdim, pk.rows, pk.chan_pad, pk.chan_real = pks[0].kdim, cout, cin, cin
+        pk = ops.PackedWeight(torch.cat([q.buf for q in pks]), cout, pks[0].kdim, cin, groups=groups,
+                              group_stride=pks[0].buf.numel())
     else:
         x = torch.randn(n, h, w, cin, generator=g).to(DEV)
         oh, ow = ops.conv_out_size(h, k, s, p), ops.conv_out_size(w, k, s, p)
@@ -1298,8 +1295,7 @@ def test_bstream_kernel_is_bit_identical_to_the_tiled_kernel(ops, case, monkeypa
         monkeypatch.setenv('HND_DEBUG_PICKER', '' if mode == '0' else 'bstream_all')
         if groups > 1:
             l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
-                              cout=cout)
-            l.desc.w_group_rows, l.desc.w_group_stride = tiles_pad, pks[0].buf.numel()
+                              cout=cout, w_group_rows=tiles_pad)
         else:
             l = ops.conv_forward(x, pk, y, k, s, p, epi_scale=sc, epi_shift=sh, res1=r, mask=mk, relu=not msk,
                                  pro_scale=ps, pro_shift=pb, pro_relu=pro)

@@ -55,10 +55,8 @@ def main():
             x = torch.randn(1, 1, groups * tiles_pad, cin, device=dev)
             y = torch.empty(1, 1, groups * tiles_pad, cout, device=dev)
             pks = [ops.pack_weights(torch.randn(cout, cin, 1, 1, device=dev) / cin ** 0.5) for _ in range(groups)]
-            pk = ops.PackedWeight.__new__(ops.PackedWeight)
-            pk.buf = torch.cat([p.buf for p in pks])
-            pk.kdim, pk.rows, pk.chan_pad, pk.chan_real = pks[0].kdim, cout, cin, cin
-            stride = pks[0].buf.numel()
+            pk = ops.PackedWeight(torch.cat([p.buf for p in pks]), cout, pks[0].kdim, cin, groups=groups,
+                                  group_stride=pks[0].buf.numel())
         else:
             x = torch.randn(n, h, w, cin, device=dev)
             oh, ow = ops.conv_out_size(h, 1, s, 0), ops.conv_out_size(w, 1, s, 0)
@@ -72,9 +70,9 @@ def main():
         for mode, e1, e2 in modes:
             os.environ['HND_BRES'], os.environ['HND_BRES2'] = e1, e2
             if groups > 1:
-                l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
-                                  cout=cout)
-                l.desc.w_group_rows, l.desc.w_group_stride = tiles_pad, stride
+                with ops.emulation('off'):          # (the native kernels on a grouped operand)
+                    l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1,
+                                      bw=0, cout=cout, w_group_rows=tiles_pad)
                 l.flops = 2 * groups * tiles_pad * cout * cin
             else:
                 l = ops.conv_forward(x, pk, y, 1, s, 0, epi_scale=sc, epi_shift=sh, res1=r, relu=True, pro_scale=ps,

@@ -62,10 +62,8 @@ def main():
             x = torch.randn(1, 1, groups * tiles_pad, cin, device=dev)
             y = torch.empty(1, 1, groups * tiles_pad, cout, device=dev)
             pks = [ops.pack_weights(torch.randn(cout, cin, 1, 1, device=dev) / cin ** 0.5) for _ in range(groups)]
-            pk = ops.PackedWeight.__new__(ops.PackedWeight)
-            pk.buf = torch.cat([q.buf for q in pks])
-            pk.kdim, pk.rows, pk.chan_pad, pk.chan_real = pks[0].kdim, cout, cin, cin
-            stride = pks[0].buf.numel()
+            pk = ops.PackedWeight(torch.cat([q.buf for q in pks]), cout, pks[0].kdim, cin, groups=groups,
+                                  group_stride=pks[0].buf.numel())
         else:
             x = torch.randn(n, h, w, cin, device=dev)
             oh, ow = ops.conv_out_size(h, k, s, p), ops.conv_out_size(w, k, s, p)
@@ -85,9 +83,9 @@ def main():
             os.environ['HND_BSTREAM'] = '1' if e2 == 'all' else e2      # 'all' = HND_DEBUG_PICKER=bstream_all
             os.environ['HND_DEBUG_PICKER'] = 'bstream_all' if e2 == 'all' else ''
             if groups > 1:
-                l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
-                                  cout=cout)
-                l.desc.w_group_rows, l.desc.w_group_stride = tiles_pad, stride
+                with ops.emulation('off'):          # (the native kernels on a grouped operand)
+                    l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1,
+                                      bw=0, cout=cout, w_group_rows=tiles_pad)
                 l.flops = 2 * groups * tiles_pad * cout * cin
             else:
                 l = ops.conv_forward(x, pk, y, k, s, p, epi_scale=sc, epi_shift=sh, res1=r, mask=mk, relu=not msk,

@@ -37,18 +37,17 @@ def main():
         x = torch.randn(1, 1, groups * tiles_pad, cin, generator=g).to(dev)
         y = torch.empty(1, 1, groups * tiles_pad, cout, device=dev)
         pks = [ops.pack_weights((torch.randn(cout, cin, 1, 1, generator=g) / cin ** 0.5).to(dev)) for _ in range(groups)]
-        pk = ops.PackedWeight.__new__(ops.PackedWeight)
-        pk.buf = torch.cat([q.buf for q in pks])
-        pk.kdim, pk.rows, pk.chan_pad, pk.chan_real = pks[0].kdim, cout, cin, cin
+        pk = ops.PackedWeight(torch.cat([q.buf for q in pks]), cout, pks[0].kdim, cin, groups=groups,
+                              group_stride=pks[0].buf.numel())
         outs, variants = {}, {}
         for mode, env in (('tiled', {'HND_BRES': '0', 'HND_BSTREAM': '0'}), ('default', {}),
                           ('bstream', {'HND_BRES': '0', 'HND_DEBUG_PICKER': 'bstream_all'})):
             for key in ('HND_BRES', 'HND_BSTREAM', 'HND_DEBUG_PICKER'):
                 os.environ.pop(key, None)
             os.environ.update(env)
-            l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
-                              cout=cout)
-            l.desc.w_group_rows, l.desc.w_group_stride = tiles_pad, pks[0].buf.numel()
+            with ops.emulation('off'):              # (the native kernels on a grouped operand, in either family)
+                l = ops.conv_desc(x, pk, y, kh=1, kw=1, oh=1, ow=groups * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
+                                  cout=cout, w_group_rows=tiles_pad)
             l.refresh_variant()
             y.fill_(float('nan'))
             l.run()
