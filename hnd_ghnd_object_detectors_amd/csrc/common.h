@@ -61,6 +61,8 @@ inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
 //   wgrad_ring_taps   the ring weight-gradient kernel also for tap (direct 2x2) problems
 //   bstream_k1024 / bstream_parity   the B-streamed kernel also for K = 1024 -> 256 launches / for stride-2 parity launches
 //   bxs_wn1                          (B-streamed emulation kernel) the 256 x 64 tile also where the output has 128-column blocks
+//   bx3_tiled=1 / bx3_tiled=0        (emulation, B resident) the tiled build wherever bx3_applies / never; both builds give
+//                                    the same bits.  bx3_tiled_mi=1|2: its 64- or 128-row tile (tools/bench_bx3_tiled.py)
 // Returns -1 when `key` is absent, its value (1 without "=value") otherwise.  Read per call: in-process A/B.
 inline int debug_picker(const char* key) {
   const char* e = getenv("HND_DEBUG_PICKER");

@@ -497,11 +497,52 @@ static int launch_bx3_one(const hnd_conv_desc& d, int kpart, hipStream_t stream)
   }
 }
 
+int launch_bx3_tiled(const hnd_conv_desc& d, int mi, hipStream_t stream);      // conv_bx3_tiled.hip
+
+// The emulated family's pick_tile: which BUILD runs a launch bx3_applies admits -- 0 the persistent kernel above, or the tiled
+// one (conv_bx3_tiled.hip) with a 64-row (1) / 128-row (2) tile.  Both give the same bits, so this is a cost decision only and
+// may read the launch's row count.  The persistent kernel pays a slice load and a ramp per team and per 256-k pass and
+// leaves CUs idle when a team gets few 64-row chunks; the tiled build pays a B stage per tile and runs at 0.6 - 0.9 x on
+// large grids.  Rule: chunks per team = ceil(ceil(M / 64) / teams) below a crossover T(K) -> tiled.
+// MEASURED (profiles/r07_bx3_tiled_shapes.txt, tools/bench_bx3_tiled.py; persistent ms / tiled ms at chunks per team c):
+//   K = 128      64-row tile 1.18 (c = 0.5) 1.11 (2) 1.04 (3) 1.00 (4) 0.85 (8)                      -> T = 3
+//   K = 256      64-row tile 1.26 (0.5) 1.11 (2) 0.99 (3) 0.95 (4) 0.81 (8)                           -> T = 3
+//   K = 512      64-row tile 1.69 (0.5) 1.30 (3) 1.15 (6) 1.13 / 1.22 (8.2: layer2.x.conv1, layer4.x.conv3 at batch 4)
+//                0.90 (12) 0.95 - 0.99 (16.4)                                                         -> T = 10
+//   K >= 1024    64-row tile 2.0 (<= 1) 1.51 (4.1) 1.23 - 1.30 (8.2) 0.99 / 1.10 (12);  128-row tile 1.12 / 1.18 (12)
+//                1.06 / 1.14 (16) 1.01 - 1.03 (16.4 - 16.5: the step's launches) 0.98 / 1.03 (24)     -> T = 16, 128 rows from 10
+// K = 768 / 1536 were not measured: 768 takes the K = 512 row, 1536 the long one.  Grouped launches (the Winograd component
+// GEMMs) were not measured either and stay on the persistent build; HND_DEBUG_PICKER=bx3_tiled=1 runs them tiled.
+static const int BX3_TILED_BELOW_K128 = 3, BX3_TILED_BELOW_K256 = 3, BX3_TILED_BELOW_K512 = 10, BX3_TILED_BELOW_KLONG = 16;
+static const int BX3_TILED_128_ROWS_FROM = 10;
+
+// 0 = persistent, 1 / 2 = tiled with a 64- / 128-row tile
+static int bx3_pick(const hnd_conv_desc& d) {
+  if (!bx3_applies(d)) return 0;
+  const long long M = (long long)d.n * d.oh * d.ow, chunks = (M + 63) / 64;
+  const long long nteams = 8ll * ((cu_count_bx3() / 8) / (d.cout / 64));
+  const long long per_team = (chunks + nteams - 1) / nteams;
+  const bool is_long = d.kdim >= 1024;
+  const int rows = is_long && per_team >= BX3_TILED_128_ROWS_FROM ? 2 : 1;
+  const int forced = debug_picker("bx3_tiled");
+  if (forced >= 0) {
+    const int mi = debug_picker("bx3_tiled_mi");
+    return forced ? (mi == 1 || mi == 2 ? mi : rows) : 0;
+  }
+  if (d.w_group_rows > 0) return 0;
+  const int below = d.kdim <= 128 ? BX3_TILED_BELOW_K128
+                                  : (d.kdim <= 256 ? BX3_TILED_BELOW_K256 : (is_long ? BX3_TILED_BELOW_KLONG : BX3_TILED_BELOW_K512));
+  return per_team < below ? rows : 0;
+}
+
+int bx3_build(const hnd_conv_desc& d) { return bx3_pick(d) ? 1 : 0; }
+
 int launch_bx3(const hnd_conv_desc& d, hipStream_t stream) {
   if (!bx3_applies(d)) {
     set_error("launch_bx3: descriptor not eligible");
     return HND_ERR_INVALID;
   }
+  if (const int rows = bx3_pick(d)) return launch_bx3_tiled(d, rows, stream);
   if (d.kdim <= 256) return launch_bx3_one(d, d.kdim, stream);
   // K = 256 P: the resident slice of three planes holds 256 k.  Pass 1: k 0 .. 255, y = acc * scale + shift (+ the launch's
   // own residual; no ReLU, no mask); pass p: k 256 (p - 1) .. with res1 = y: y = acc * scale + y; the last pass applies the

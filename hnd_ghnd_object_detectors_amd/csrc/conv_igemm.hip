@@ -588,6 +588,7 @@ int launch_bstream(const hnd_conv_desc& d, hipStream_t stream);
 size_t bstream_workspace(const hnd_conv_desc& d);
 bool bx3_applies(const hnd_conv_desc& d);                      // conv_bx3.hip: fp32 emulated on the bf16 pipe, B resident
 int launch_bx3(const hnd_conv_desc& d, hipStream_t stream);
+int bx3_build(const hnd_conv_desc& d);                         // ... its persistent (0) or tiled (1) build: the same bits
 int bxs_variant(const hnd_conv_desc& d);                       // conv_bxs.hip: ... B streamed (taps, long K, any epilogue)
 int launch_bxs(const hnd_conv_desc& d, hipStream_t stream);
 size_t bxs_workspace(const hnd_conv_desc& d);
@@ -656,4 +657,10 @@ extern "C" int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc) {
   if (const int v = hnd::bres_variant(*desc)) return v == 2 ? 5 : (v == 1 ? 6 : (v == 4 ? 7 : 8));
   if (const int v = hnd::bstream_variant(*desc)) return v == 2 ? 11 : 12;
   return pick_tile(*desc);
+}
+
+extern "C" int hnd_conv2d_igemm_build(const hnd_conv_desc* desc) {
+  if (!desc) return -1;
+  if (desc->cin == 4 || thin_n_applies(*desc)) return 0;
+  return hnd::bx3_build(*desc);
 }

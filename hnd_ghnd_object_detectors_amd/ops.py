@@ -240,7 +240,7 @@ def fbn_fold(weight, bias, mean, var, eps=0.0, cs=None, out=None):
 # --------------------------------------------------------------------------------------- conv launches
 class ConvLaunch(object):
     """One prebuilt hnd_conv2d_igemm launch (descriptor + keep-alive references)."""
-    __slots__ = ('desc', 'ref', 'keep', 'flops', 'alg_flops', 'variant', 'relay')
+    __slots__ = ('desc', 'ref', 'keep', 'flops', 'alg_flops', 'variant', 'build', 'relay')
 
     def __init__(self, desc, keep, flops=0):
         self.desc, self.keep, self.flops = desc, keep, flops
@@ -264,6 +264,8 @@ class ConvLaunch(object):
             ('igemm_128x128', 'igemm_128x64', 'igemm_64x128', 'igemm_64x64', 'thin_n4', 'bres_128',
              'bres_64', 'bres2_128', 'bres2_64', 'stem7_lds', 'unused', 'bstream_128', 'bstream_64', 'bx3_64',
              'bxs_128', 'bxs_64')[tile]
+        # which build of that kernel (the emulation kernel has two that give the same bits); None: no such distinction
+        self.build = ('persistent', 'tiled')[int(_L.hnd_conv2d_igemm_build(self.ref))] if tile == 13 else None
 
     def run(self, stream=None):
         rc = _L.hnd_conv2d_igemm(self.ref, stream if stream is not None else stream_ptr())

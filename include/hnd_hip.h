@@ -167,6 +167,12 @@ size_t hnd_conv2d_igemm_workspace(const hnd_conv_desc* desc);
  * HND_BSTREAM=0 turns it off). */
 int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc);      /* (13 = the bf16x3 emulation kernel, csrc/conv_bx3.hip; 14 / 15 =
                                                              * its B-streamed build, 128 x 128 / 256 x 64 tile, csrc/conv_bxs.hip) */
+/* which BUILD of the kernel named by hnd_conv2d_igemm_tile runs this launch: 0 = the only / the persistent build, 1 = the
+ * tiled build of the bf16x3 emulation kernel (tile 13, csrc/conv_bx3_tiled.hip: one workgroup per output tile, chosen where
+ * the persistent kernel's teams would get few 64-row chunks -- small batches, coarse maps); -1 on NULL.  GUARANTEE: both
+ * builds of a kernel compute IDENTICAL BITS for every launch, so the choice (which may read the launch's batch) is
+ * invisible in every result.  HND_DEBUG_PICKER=bx3_tiled=1 / =0 forces one of them. */
+int hnd_conv2d_igemm_build(const hnd_conv_desc* desc);
 /* ABI 12: should a layer's launches carry a weight image (run on the emulation)?  Decided from the LAYER alone: GEMM rows ONE
  * image contributes (oh * ow of a 1x1 conv; components x tiles of a Winograd launch), depth and output channels -- priced
  * at 16 images per GPU, never at the launch's own batch.  1 = attach hnd_conv_desc.w_bf16x3, 0 = leave it NULL. */

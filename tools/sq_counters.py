@@ -21,6 +21,9 @@ from collections import defaultdict
 def waves_per_simd(name):
     if 'bres2_kernel' in name or 'bstream_kernel' in name or 'wgrad_ring' in name or 'bx3_kernel' in name or 'bxs_kernel' in name:
         return 1
+    m = re.search(r'bx3t_kernel<(\d+)>', name)
+    if m:       # tiled build of the bf16x3 emulation GEMM: 3 workgroups per CU with the 64-row tile, 2 with the 128-row one
+        return 3 if m.group(1) == '1' else 2
     if 'bres_kernel' in name:
         return 2
     m = re.search(r'igemm_kernel<(\d+), (\d+)', name)

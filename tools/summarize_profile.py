@@ -33,6 +33,9 @@ def short(name):
         return 'bx3_64' + ('[K%d%s%s%s]' % (32 * int(m.group(1)), ', res' if m.group(2) == 'true' else '',
                                             ', bits out' if m.group(3) == 'true' else '', ', bits in' if m.group(4) == 'true' else '')
                            if FULLNAMES else '')
+    m = re.search(r'bx3t_kernel<(\d+)>', name)
+    if m:           # ... its tiled build (conv_bx3_tiled.hip): same family member, 64 / 128-row tile
+        return 'bx3_64' + ('[tiled %d rows]' % (64 * int(m.group(1))) if FULLNAMES else '')
     m = re.search(r'bxs_kernel<(\d+), (true|false), (true|false)>', name)
     if m:           # ... B streamed (conv_bxs.hip)
         return 'bxs_%d' % (64 * int(m.group(1))) + (('[prologue]' if m.group(2) == 'true' else '') +
