@@ -58,6 +58,15 @@ class MsePair(C.Structure):
                 ('factor', C.c_float), ('relu_mask', C.c_int32)]
 
 
+class MimicPair(C.Structure):
+    """struct hnd_mimic_pair"""
+    _fields_ = [('teacher', vp), ('student', vp), ('grad', vp), ('numel', C.c_int64), ('count', C.c_int64),
+                ('factor', C.c_float), ('param', C.c_float), ('kind', C.c_int32), ('relu_mask', C.c_int32)]
+
+
+MIMIC_KINDS = {'mse': 0, 'l1': 1, 'smooth_l1': 2, 'huber': 3}        # enum hnd_mimic_kind
+
+
 _SIGNATURES = {
     'hnd_last_error_string': (C.c_char_p, []),
     'hnd_abi_version': (C.c_int, []),
@@ -113,6 +122,7 @@ _SIGNATURES = {
     'hnd_bn_bwd_apply': (C.c_int, [vp] * 5 + [C.c_int, vp, C.c_int64, C.c_int, vp]),
     'hnd_mse_scratch_elems': (C.c_size_t, []),
     'hnd_mse_sum_fwd_bwd': (C.c_int, [C.POINTER(MsePair), C.c_int, vp, vp, vp]),
+    'hnd_mimic_loss_fwd_bwd': (C.c_int, [C.POINTER(MimicPair), C.c_int, vp, vp, vp]),
     'hnd_scale_by_device_scalar': (C.c_int, [vp, C.c_int64, vp, vp]),
     'hnd_adam_step_flat': (C.c_int, [vp, vp, vp, vp, C.c_int64] + [C.c_float] * 4 + [C.c_int64, C.c_float, vp]),
     'hnd_subsample2': (C.c_int, [vp, vp] + [C.c_int] * 6 + [vp]),

@@ -5,6 +5,7 @@
 #include "common.h"
 
 #include <hip/hip_fp16.h>
+#include <float.h>
 #include <math.h>
 
 namespace {
@@ -597,6 +598,23 @@ struct MseArgs {
   int npairs;
 };
 
+// The workgroups of a loss launch, split among its pairs by size (both entry points: the reduction order of a pair, and so
+// its bits, follows from its block count).  Fills first_block[0..npairs]; returns the grid size.
+template <class Pair>
+static int loss_split_blocks(const Pair* pairs, int npairs, long long total, int* first_block) {
+  int used = 0;
+  for (int k = 0; k < npairs; ++k) {
+    first_block[k] = used;
+    long long nb = (long long)(kMseBlocks - npairs) * pairs[k].numel / total + 1;
+    const long long maxb = (pairs[k].numel / 4 + 256 * kEwU - 1) / (256 * kEwU);
+    if (nb > maxb) nb = maxb;
+    if (nb < 1) nb = 1;
+    used += (int)nb;
+  }
+  first_block[npairs] = used;
+  return used;
+}
+
 __global__ void mse_kernel(const MseArgs a, double* __restrict__ scratch) {
   __shared__ double wsum[4];
   int k = 0;
@@ -654,6 +672,162 @@ __global__ void mse_finalize_kernel(const MseArgs a, const double* __restrict__ 
     if (lane == 0) {
       term[k] = s * (double)a.pair[k].factor;
       out[1 + k] = term[k];
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+    for (int i = 0; i < a.npairs; ++i) tot += term[i];
+    out[0] = tot;
+  }
+}
+
+// Generalised mimic loss (hnd_mimic_loss_fwd_bwd): the loop of mse_kernel with the elementwise criterion as a template
+// parameter.  A workgroup belongs to one pair, so the kind is selected ONCE, outside the chunk loop (a switch over the
+// instantiations below); inside the loop the two zones of SmoothL1 / Huber are a compare and a select per element, never
+// a branch.  d = s - t; the host folds factor, 1/count, 1/beta and delta into the fp32 constants of the pair.
+struct MimicDev {
+  const float* teacher;
+  const float* student;
+  float* grad;
+  long long numel;
+  double term_scale;      // factor (sum) -- applied in finalize, in double
+  double term_div;        // count of a mean-reduced term, 0 = sum
+  float gq, gl;           // gradient: gq * d in the quadratic zone (MSE: everywhere), gl * sign(d) in the linear one
+  float thr;              // beta / delta
+  float vq, vl, vc;       // value: vq * d * d in the quadratic zone, vl * |d| + vc (one fma) in the linear one
+  int kind, relu_mask;
+};
+struct MimicArgs {
+  MimicDev pair[kMaxPairs];
+  int first_block[kMaxPairs + 1];
+  int npairs;
+};
+
+template <int KIND> struct MimicOp;
+template <> struct MimicOp<HND_MIMIC_MSE> {
+  static __device__ __forceinline__ float sum4(const f32x4 df, const MimicDev&) {
+    return (df.x * df.x + df.y * df.y) + (df.z * df.z + df.w * df.w);
+  }
+  static __device__ __forceinline__ f32x4 grad4(const f32x4 df, const MimicDev& P) { return df * P.gq; }
+};
+// (Both sides of every `?:` below are locals computed unconditionally: the compiler then emits a select (v_cndmask).  With
+// the arithmetic inside the arms it built divergent branches -- s_and_saveexec per element -- in the unrolled loop.)
+template <> struct MimicOp<HND_MIMIC_L1> {
+  static __device__ __forceinline__ float sum4(const f32x4 df, const MimicDev&) {
+    return (fabsf(df.x) + fabsf(df.y)) + (fabsf(df.z) + fabsf(df.w));
+  }
+  static __device__ __forceinline__ float g1(float d, float gl) {
+    const float signed_gl = copysignf(gl, d);
+    return d != 0.f ? signed_gl : 0.f;
+  }
+  static __device__ __forceinline__ f32x4 grad4(const f32x4 df, const MimicDev& P) {
+    const float gl = P.gl;
+    f32x4 g;
+    g.x = g1(df.x, gl); g.y = g1(df.y, gl); g.z = g1(df.z, gl); g.w = g1(df.w, gl);
+    return g;
+  }
+};
+// SmoothL1: |d| < beta is the quadratic zone; Huber: |d| <= delta.  (At the threshold both zones give the same value and
+// the same gradient, so the two differ only in which formula rounds it.  d = 0 is in the quadratic zone, or -- Huber with
+// delta = 0 -- has a linear-zone gradient of gl = 0: sign(0) never matters.)
+template <bool INCLUSIVE> struct MimicTwoZone {
+  struct K { float thr, vq, vl, vc, gq, gl; };
+  static __device__ __forceinline__ void one(float d, const K& k, float& v, float& g) {
+    const float ad = fabsf(d);
+    const bool quad = INCLUSIVE ? ad <= k.thr : ad < k.thr;
+    const float vquad = k.vq * d * d, vlin = fmaf(k.vl, ad, k.vc);
+    const float gquad = k.gq * d, glin = copysignf(k.gl, d);
+    v = quad ? vquad : vlin;
+    g = quad ? gquad : glin;
+  }
+  static __device__ __forceinline__ float sum4_grad4(const f32x4 df, const MimicDev& P, f32x4& g) {
+    const K k = {P.thr, P.vq, P.vl, P.vc, P.gq, P.gl};
+    float vx, vy, vz, vw, gx, gy, gz, gw;
+    one(df.x, k, vx, gx); one(df.y, k, vy, gy); one(df.z, k, vz, gz); one(df.w, k, vw, gw);
+    g.x = gx; g.y = gy; g.z = gz; g.w = gw;
+    return (vx + vy) + (vz + vw);
+  }
+  static __device__ __forceinline__ float sum4(const f32x4 df, const MimicDev& P) {
+    f32x4 g;
+    return sum4_grad4(df, P, g);
+  }
+  static __device__ __forceinline__ f32x4 grad4(const f32x4 df, const MimicDev& P) {
+    f32x4 g;
+    sum4_grad4(df, P, g);
+    return g;
+  }
+};
+template <> struct MimicOp<HND_MIMIC_SMOOTH_L1> : MimicTwoZone<false> {};
+template <> struct MimicOp<HND_MIMIC_HUBER> : MimicTwoZone<true> {};
+
+template <int KIND>
+__device__ __forceinline__ float mimic_chunks(const MimicDev& P, int nb, int lb) {
+  const long long n4 = P.numel >> 2;
+  float acc = 0.f;
+  // (same traversal and the same fixed summation order as mse_kernel)
+  const long long chunk = 256ll * kEwU;
+  for (long long base = (long long)lb * chunk + threadIdx.x; base < n4; base += (long long)nb * chunk) {
+    f32x4 tv[kEwU], sv[kEwU];
+#pragma unroll
+    for (int u = 0; u < kEwU; ++u) {
+      const long long e = base + 256ll * u;
+      if (e < n4) {
+        tv[u] = *(const f32x4*)(P.teacher + e * 4);
+        sv[u] = *(const f32x4*)(P.student + e * 4);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kEwU; ++u) {
+      const long long e = base + 256ll * u;
+      if (e >= n4) continue;
+      const f32x4 s = sv[u];
+      const f32x4 df = s - tv[u];
+      acc += MimicOp<KIND>::sum4(df, P);
+      if (P.grad) {
+        f32x4 gg = MimicOp<KIND>::grad4(df, P);
+        if (P.relu_mask) {
+          gg.x = s.x > 0.f ? gg.x : 0.f; gg.y = s.y > 0.f ? gg.y : 0.f;
+          gg.z = s.z > 0.f ? gg.z : 0.f; gg.w = s.w > 0.f ? gg.w : 0.f;
+        }
+        *(f32x4*)(P.grad + e * 4) = gg;
+      }
+    }
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(256) mimic_kernel(const MimicArgs a, double* __restrict__ scratch) {
+  __shared__ double wsum[4];
+  int k = 0;
+  while (k + 1 < a.npairs && (int)blockIdx.x >= a.first_block[k + 1]) ++k;
+  const MimicDev P = a.pair[k];
+  const int nb = a.first_block[k + 1] - a.first_block[k], lb = blockIdx.x - a.first_block[k];
+  float acc;
+  switch (P.kind) {
+    case HND_MIMIC_L1: acc = mimic_chunks<HND_MIMIC_L1>(P, nb, lb); break;
+    case HND_MIMIC_SMOOTH_L1: acc = mimic_chunks<HND_MIMIC_SMOOTH_L1>(P, nb, lb); break;
+    case HND_MIMIC_HUBER: acc = mimic_chunks<HND_MIMIC_HUBER>(P, nb, lb); break;
+    default: acc = mimic_chunks<HND_MIMIC_MSE>(P, nb, lb); break;
+  }
+  double dsum = wave_sum_d((double)acc);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = dsum;
+  __syncthreads();
+  if (threadIdx.x == 0) scratch[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+__global__ void mimic_finalize_kernel(const MimicArgs a, const double* __restrict__ scratch, double* __restrict__ out) {
+  __shared__ double term[kMaxPairs];
+  const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (k < a.npairs) {
+    double s = 0.0;
+    for (int b = a.first_block[k] + lane; b < a.first_block[k + 1]; b += 64) s += scratch[b];
+    s = wave_sum_d(s);
+    if (lane == 0) {
+      double t = s * a.pair[k].term_scale;
+      if (a.pair[k].term_div != 0.0) t /= a.pair[k].term_div;
+      term[k] = t;
+      out[1 + k] = t;
     }
   }
   __syncthreads();
@@ -1100,22 +1274,67 @@ int hnd_mse_sum_fwd_bwd(const hnd_mse_pair* pairs, int npairs, double* loss_out,
     a.pair[k] = pairs[k];
     total += pairs[k].numel;
   }
-  int used = 0;
-  for (int k = 0; k < npairs; ++k) {
-    a.first_block[k] = used;
-    long long nb = (long long)(kMseBlocks - npairs) * pairs[k].numel / total + 1;
-    const long long maxb = (pairs[k].numel / 4 + 256 * kEwU - 1) / (256 * kEwU);
-    if (nb > maxb) nb = maxb;
-    if (nb < 1) nb = 1;
-    used += (int)nb;
-  }
-  a.first_block[npairs] = used;
+  const int used = loss_split_blocks(pairs, npairs, total, a.first_block);
   hipStream_t s = hnd::as_stream(stream);
   hipLaunchKernelGGL(mse_kernel, dim3(used), dim3(256), 0, s, a, scratch);
   int rc = hnd::check_launch("hnd_mse_sum_fwd_bwd");
   if (rc) return rc;
   hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(64 * kMaxPairs), 0, s, a, scratch, loss_out);
   return hnd::check_launch("hnd_mse_sum_fwd_bwd(finalize)");
+}
+
+int hnd_mimic_loss_fwd_bwd(const hnd_mimic_pair* pairs, int npairs, double* loss_out, double* scratch, void* stream) {
+  HND_REQUIRE(pairs && loss_out && scratch, "hnd_mimic_loss_fwd_bwd: null pointer");
+  HND_REQUIRE(npairs >= 1 && npairs <= kMaxPairs, "hnd_mimic_loss_fwd_bwd: 1..%d pairs supported", kMaxPairs);
+  MimicArgs a;
+  a.npairs = npairs;
+  long long total = 0;
+  for (int k = 0; k < npairs; ++k) {
+    const hnd_mimic_pair& p = pairs[k];
+    HND_REQUIRE(p.teacher && p.student && p.numel > 0 && p.numel % 4 == 0,
+                "hnd_mimic_loss_fwd_bwd: pair %d invalid (numel must be a positive multiple of 4)", k);
+    HND_REQUIRE(p.kind >= HND_MIMIC_MSE && p.kind <= HND_MIMIC_HUBER, "hnd_mimic_loss_fwd_bwd: pair %d: unknown kind %d",
+                k, (int)p.kind);
+    HND_REQUIRE(p.param >= 0.f && p.param <= FLT_MAX,
+                "hnd_mimic_loss_fwd_bwd: pair %d: beta / delta must be finite and >= 0", k);
+    HND_REQUIRE(p.count >= 0 && p.count <= p.numel,
+                "hnd_mimic_loss_fwd_bwd: pair %d: count must be 0 (sum) or the logical element count (1..numel)", k);
+    MimicDev& d = a.pair[k];
+    d.teacher = p.teacher; d.student = p.student; d.grad = p.grad; d.numel = p.numel;
+    d.relu_mask = p.relu_mask;
+    d.term_scale = (double)p.factor;
+    d.term_div = (double)p.count;
+    // one fp32 weight per pair, computed in double and rounded once
+    const double wd = p.count ? (double)p.factor / (double)p.count : (double)p.factor;
+    const float w = (float)wd;
+    const double thr = (double)p.param;
+    // beta = 0 IS L1 (torch); so is a denormal beta, whose 1 / beta has no fp32 value
+    d.kind = (p.kind == HND_MIMIC_SMOOTH_L1 && p.param < FLT_MIN) ? (int)HND_MIMIC_L1 : (int)p.kind;
+    d.thr = p.param;
+    d.gq = d.gl = d.vq = d.vl = d.vc = 0.f;
+    switch (d.kind) {
+      case HND_MIMIC_MSE: d.gq = 2.f * w; break;
+      case HND_MIMIC_L1: d.gl = w; break;
+      case HND_MIMIC_SMOOTH_L1:
+        d.gq = (float)(wd / thr); d.gl = w;
+        d.vq = (float)(0.5 / thr); d.vl = 1.f; d.vc = (float)(-0.5 * thr);
+        break;
+      default:      // HND_MIMIC_HUBER
+        d.gq = w; d.gl = (float)(wd * thr);
+        d.vq = 0.5f; d.vl = p.param; d.vc = (float)(-0.5 * thr * thr);
+        break;
+    }
+    HND_REQUIRE(fabsf(d.gq) <= FLT_MAX && fabsf(d.gl) <= FLT_MAX && fabsf(d.vq) <= FLT_MAX && fabsf(d.vc) <= FLT_MAX,
+                "hnd_mimic_loss_fwd_bwd: pair %d: factor / count / beta / delta give a weight outside fp32", k);
+    total += p.numel;
+  }
+  const int used = loss_split_blocks(pairs, npairs, total, a.first_block);
+  hipStream_t s = hnd::as_stream(stream);
+  hipLaunchKernelGGL(mimic_kernel, dim3(used), dim3(256), 0, s, a, scratch);
+  int rc = hnd::check_launch("hnd_mimic_loss_fwd_bwd");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mimic_finalize_kernel, dim3(1), dim3(64 * kMaxPairs), 0, s, a, scratch, loss_out);
+  return hnd::check_launch("hnd_mimic_loss_fwd_bwd(finalize)");
 }
 
 int hnd_scale_by_device_scalar(float* x, int64_t numel, const float* scale_dev, void* stream) {

@@ -1,6 +1,7 @@
-"""Fused L2 feature-mimic loss on the HIP path.
+"""Fused feature-mimic loss on the HIP path.
 
-``HipMSELoss`` is what ``func_util.get_loss('MSELoss', {'reduction': 'sum'})`` returns;
+``HipMSELoss`` / ``HipL1Loss`` / ``HipSmoothL1Loss`` / ``HipHuberLoss`` are what ``func_util.get_loss`` returns for the
+elementwise criteria of a YAML (``reduction`` 'sum' or 'mean');
 ``distill_loss`` fuses all terms of GeneralizedCustomLoss (reference src/distillation/loss.py:27-33) into ONE
 launch that produces the scalar loss and, in the same pass over the features, the gradient w.r.t. every
 student tensor.  ``loss.backward()`` then replays the hand-written backward plan of the student
@@ -17,16 +18,70 @@ from .. import ops
 from ..hipnn import to_nhwc
 
 
-class HipMSELoss(nn.Module):
+SUPPORTED_CRITERIA = ("MSELoss, L1Loss, SmoothL1Loss(beta), HuberLoss(delta), each with reduction='sum' or 'mean' "
+                      "(elementwise criteria that are symmetric in their two arguments; one fused HIP launch for all terms)")
+
+
+class _HipElementwiseLoss(nn.Module):
+    """A criterion of the fused loss launch: carries (kind, param, reduction).  `kind` is a key of _lib.MIMIC_KINDS, `param`
+    the beta of SmoothL1 / delta of Huber."""
+    kind, param = None, 0.0
+
     def __init__(self, reduction='mean', size_average=None, reduce=None):
         super().__init__()
-        if reduction != 'sum':
-            raise NotImplementedError("HIP path implements MSELoss(reduction='sum') (all hnd/ghnd configs)")
+        if size_average is not None or reduce is not None:
+            raise NotImplementedError("%s: the legacy size_average / reduce arguments are not taken; say reduction='sum' or "
+                                      "'mean'.  Supported: %s" % (type(self).__name__[3:], SUPPORTED_CRITERIA))
+        if reduction not in ('sum', 'mean'):
+            raise NotImplementedError('%s(reduction=%r) is not built (the loss is reduced inside the launch).  Supported: %s'
+                                      % (type(self).__name__[3:], reduction, SUPPORTED_CRITERIA))
         self.reduction = reduction
+
+    def is_mse_sum(self):
+        return self.kind == 'mse' and self.reduction == 'sum'
+
+    def extra_repr(self):
+        return 'reduction=%r' % self.reduction + (', param=%g' % self.param if self.kind in ('smooth_l1', 'huber') else '')
 
     def forward(self, input, target):
         """standalone use: (teacher, student) -> loss with gradient to the student through distill_loss."""
-        return distill_loss([('term', input, target, 1.0)])
+        return distill_loss([('term', input, target, 1.0, self)])
+
+
+def _threshold(name, what, value, allow_zero):
+    value = float(value)
+    if not (value >= 0.0 and value != float('inf')) or (value == 0.0 and not allow_zero):
+        raise ValueError('%s: %s must be a finite number %s 0, got %r' % (name, what, '>=' if allow_zero else '>', value))
+    return value
+
+
+class HipMSELoss(_HipElementwiseLoss):
+    kind = 'mse'
+
+
+class HipL1Loss(_HipElementwiseLoss):
+    kind = 'l1'
+
+
+class HipSmoothL1Loss(_HipElementwiseLoss):
+    kind = 'smooth_l1'
+
+    def __init__(self, reduction='mean', beta=1.0, size_average=None, reduce=None):
+        super().__init__(reduction, size_average, reduce)
+        self.param = self.beta = _threshold('SmoothL1Loss', 'beta', beta, True)        # (beta = 0 is L1Loss, as in torch)
+
+
+class HipHuberLoss(_HipElementwiseLoss):
+    """delta must be positive, as torch.nn.HuberLoss documents: that rule is this class's.  (The C entry point takes
+    delta = 0 as well -- the loss is then identically zero -- so a caller of the ABI is not held to torch's wording.)"""
+    kind = 'huber'
+
+    def __init__(self, reduction='mean', delta=1.0):
+        super().__init__(reduction)
+        self.param = self.delta = _threshold('HuberLoss', 'delta', delta, False)
+
+
+_MSE_SUM = HipMSELoss(reduction='sum')
 
 
 class GradArena(object):
@@ -142,9 +197,16 @@ def _student_position(src, body):
 
 
 def distill_loss(terms):
-    """terms: list of (name, teacher_out, student_out, factor).  Returns a 0-dim float32 loss tensor.
+    """terms: list of (name, teacher_out, student_out, factor[, criterion]); the criterion is one of the Hip*Loss modules
+    above, absent = MSELoss(reduction='sum').  Returns a 0-dim float32 loss tensor.
     Teacher tensors may be ANY tensor produced by the HIP path; student tensors are located in the backward plan by
     their ``_hnd_src`` tag (see _student_position)."""
+    crits = [t[4] if len(t) > 4 and t[4] is not None else _MSE_SUM for t in terms]
+    for c in crits:
+        if not isinstance(c, _HipElementwiseLoss):
+            raise NotImplementedError('criterion %r does not run on the HIP path.  Supported: %s'
+                                      % (type(c).__name__, SUPPORTED_CRITERIA))
+    terms = [tuple(t[:4]) for t in terms]
     srcs = [getattr(s, '_hnd_src', None) for _, _, s, _ in terms]
     # a pyramid map on the student side is tagged ('fpn', 'layer_blocks', level, FeaturePyramidNetwork module, engine)
     is_fpn = [src is not None and isinstance(src[0], str) and src[0] == 'fpn' for src in srcs]
@@ -225,10 +287,17 @@ def distill_loss(terms):
         raise NotImplementedError('two loss terms on the same (top) student tensor')
     key = tuple((p[0].data_ptr(), p[1].data_ptr(), None if p[2] is None else p[2].data_ptr(), p[3], p[4])
                 for p in pairs)
-    cache = getattr(body, '_mse_cache', None)
+    general = not all(c.is_mse_sum() for c in crits)
+    if general:
+        # any other criterion: ALL terms go through the general entry point (still one launch + one finalize).  A mean
+        # divides by the LOGICAL element count of the hooked tensor, not by the buffer's (padded channels)
+        pairs = [p + (c.kind, c.param, s_out.numel() if c.reduction == 'mean' else 0)
+                 for p, c, (_, _, s_out, _) in zip(pairs, crits, terms)]
+        key = ('mimic',) + tuple(k + p[5:] for k, p in zip(key, pairs))
+    cache = getattr(body, '_loss_cache', None)          # (key, ops.MseLaunch or ops.MimicLaunch)
     if cache is None or cache[0] != key:
-        cache = (key, ops.MseLaunch(pairs, dev))
-        body._mse_cache = cache
+        cache = (key, (ops.MimicLaunch if general else ops.MseLaunch)(pairs, dev))
+        body._loss_cache = cache
     out = cache[1].run()
     loss_value = out[0].float()
     per_term = out[1:]

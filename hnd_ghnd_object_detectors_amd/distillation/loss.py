@@ -2,15 +2,16 @@
 
 ``criterion(output_dict, org_loss_dict)`` returns  sum_k factor_k * criterion_k(teacher_k, student_k); the
 reference adds ``org_loss_factor`` times the detector losses when that factor is non-zero (:32-34), which no
-hnd/ghnd config uses and which needs RPN / RoI heads (outside this build).  Every term is evaluated by ONE fused
-HIP launch that also writes the gradients (hip_loss.distill_loss).
+hnd/ghnd config uses and which needs RPN / RoI heads (outside this build).  Every term -- MSELoss, L1Loss, SmoothL1Loss
+or HuberLoss, reduction 'sum' or 'mean', chosen per term -- is evaluated by ONE fused HIP launch that also writes the
+gradients (hip_loss.distill_loss).
 """
 from collections import namedtuple
 
 from torch import nn
 
 from ..myutils.pytorch import func_util
-from .hip_loss import HipMSELoss, distill_loss
+from .hip_loss import distill_loss
 
 Term = namedtuple('Term', 'ts_modules criterion factor')
 
@@ -39,9 +40,7 @@ class GeneralizedCustomLoss(CustomLoss):
         fused = []
         for name, (teacher_side, student_side) in output_dict.items():
             term = self.term_dict[name]
-            if not isinstance(term.criterion, HipMSELoss):
-                raise NotImplementedError('only MSELoss(sum) terms run on the HIP path')
-            fused.append((name, teacher_side[1], student_side[1], term.factor))
+            fused.append((name, teacher_side[1], student_side[1], term.factor, term.criterion))
         return distill_loss(fused)
 
 

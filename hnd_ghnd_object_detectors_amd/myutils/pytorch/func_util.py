@@ -1,12 +1,12 @@
 """Factories the runner calls by name (src/mimic_runner.py:67-70, src/distillation/loss.py:13).
 
-get_optimizer('Adam' / 'SGD') returns the fused flat-arena optimizers, get_loss('MSELoss', reduction='sum') the fused
-HIP loss; schedulers are plain torch (host-side scalars only)."""
+get_optimizer('Adam' / 'SGD') returns the fused flat-arena optimizers, get_loss('MSELoss' / 'L1Loss' / 'SmoothL1Loss' /
+'HuberLoss', reduction 'sum' or 'mean') a criterion of the fused HIP loss; schedulers are plain torch (host-side scalars only)."""
 import torch
 from torch import nn
 
 from ...optim import FusedAdam, FusedSGD
-from ...distillation.hip_loss import HipMSELoss
+from ...distillation.hip_loss import HipMSELoss, HipL1Loss, HipSmoothL1Loss, HipHuberLoss, SUPPORTED_CRITERIA
 
 
 def get_optimizer(target, optim_type, optim_params_config):
@@ -26,9 +26,14 @@ def get_scheduler(optimizer, scheduler_type, scheduler_params_config):
     raise ValueError('scheduler_type `{}` is not expected'.format(scheduler_type))
 
 
+LOSS_DICT = {'mse': HipMSELoss, 'mseloss': HipMSELoss, 'l1': HipL1Loss, 'l1loss': HipL1Loss,
+             'smoothl1': HipSmoothL1Loss, 'smoothl1loss': HipSmoothL1Loss, 'huber': HipHuberLoss, 'huberloss': HipHuberLoss}
+
+
 def get_loss(loss_type, param_dict=None):
     param_dict = param_dict or {}
-    if loss_type.lower() in ('mse', 'mseloss'):
-        return HipMSELoss(**param_dict)
-    raise ValueError('loss_type `{}` is not expected on the HIP distillation path (the hnd/ghnd configs use '
-                     'MSELoss)'.format(loss_type))
+    cls = LOSS_DICT.get(loss_type.lower())
+    if cls is None:
+        raise ValueError('loss_type `{}` is not expected on the HIP distillation path.  Supported: {}'
+                         .format(loss_type, SUPPORTED_CRITERIA))
+    return cls(**param_dict)

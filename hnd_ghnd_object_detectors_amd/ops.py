@@ -11,7 +11,7 @@ import math
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, WgradDesc, MsePair, check
+from ._lib import ConvDesc, WgradDesc, MsePair, MimicPair, MIMIC_KINDS, check
 
 _L = _lib.load()
 # advanced by every fused optimizer step: packed-weight caches (engine.weight_version) key on it because the raw-pointer
@@ -617,6 +617,11 @@ def bn_bwd_apply(g, x, scale, shift, k123, relu, dx):
                             x.numel() // cs, cs, stream_ptr()), 'hnd_bn_bwd_apply'))
 
 
+# launches of each loss entry point so far (like HBM_PROFILE, host-side accounting only: which of the two a criterion
+# section took -- an all-MSELoss(sum) one never takes the general entry point)
+LOSS_LAUNCHES = {'hnd_mse_sum_fwd_bwd': 0, 'hnd_mimic_loss_fwd_bwd': 0}
+
+
 class MseLaunch(object):
     """Prebuilt multi-pair fused loss + gradient launch."""
 
@@ -634,9 +639,38 @@ class MseLaunch(object):
 
     def run(self):
         nbytes = sum(4 * t.numel() * (3 if g is not None else 2) for t, s, g, f, rm in self.keep)
+        LOSS_LAUNCHES['hnd_mse_sum_fwd_bwd'] += 1
         _hbm('mse', nbytes, lambda: check(
             _L.hnd_mse_sum_fwd_bwd(self.arr, self.n, ptr(self.out), ptr(self.scratch), stream_ptr()),
             'hnd_mse_sum_fwd_bwd'))
+        return self.out
+
+
+class MimicLaunch(object):
+    """MseLaunch for any elementwise criterion and either reduction (hnd_mimic_loss_fwd_bwd): same caching contract, built
+    once per set of pointers, run() returns the device double[1 + n] (total, per term)."""
+
+    def __init__(self, pairs, device):
+        """pairs: list of (teacher, student, grad_or_None, factor, relu_mask, kind, param, count); kind is a key of
+        _lib.MIMIC_KINDS, param the beta / delta, count the LOGICAL element count a mean divides by (0 = sum)."""
+        self.n = len(pairs)
+        self.arr = (MimicPair * self.n)()
+        self.keep = pairs
+        for a, (t, s, g, f, rm, kind, param, count) in zip(self.arr, pairs):
+            assert t.numel() == s.numel() and t.is_contiguous() and s.is_contiguous()
+            assert g is None or (g.numel() == s.numel() and g.is_contiguous())
+            a.teacher, a.student, a.grad = ptr(t), ptr(s), ptr(g)
+            a.numel, a.count, a.factor, a.param = t.numel(), int(count), float(f), float(param)
+            a.kind, a.relu_mask = MIMIC_KINDS[kind], int(rm)
+        self.out = torch.zeros(1 + self.n, dtype=torch.float64, device=device)
+        self.scratch = torch.empty(_L.hnd_mse_scratch_elems(), dtype=torch.float64, device=device)
+
+    def run(self):
+        nbytes = sum(4 * p[0].numel() * (3 if p[2] is not None else 2) for p in self.keep)
+        LOSS_LAUNCHES['hnd_mimic_loss_fwd_bwd'] += 1
+        _hbm('mse', nbytes, lambda: check(
+            _L.hnd_mimic_loss_fwd_bwd(self.arr, self.n, ptr(self.out), ptr(self.scratch), stream_ptr()),
+            'hnd_mimic_loss_fwd_bwd'))
         return self.out
 
 

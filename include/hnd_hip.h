@@ -423,6 +423,41 @@ typedef struct hnd_mse_pair {
 } hnd_mse_pair;
 size_t hnd_mse_scratch_elems(void);
 int hnd_mse_sum_fwd_bwd(const hnd_mse_pair* pairs, int npairs, double* loss_out, double* scratch, void* stream);
+/* The same launch for any elementwise, symmetric criterion of the YAML's `criterion` section (the reference builds each
+ * term with func_util.get_loss(type, params), src/distillation/loss.py:13) and either reduction.  With d = s - t and
+ * w = factor (count == 0: reduction='sum') or factor / count (reduction='mean'):
+ *   kind        value per element                                        gradient w.r.t. s
+ *   MSE         d^2                                                      2 w d
+ *   L1          |d|                                                      w sign(d), sign(0) = 0
+ *   SMOOTH_L1   |d| <  beta  ? 0.5 d^2 / beta : |d| - 0.5 beta           w d / beta  or  w sign(d)     (beta = 0 is L1)
+ *   HUBER       |d| <= delta ? 0.5 d^2 : delta (|d| - 0.5 delta)         w d         or  w delta sign(d)
+ * (torch's F.mse_loss / l1_loss / smooth_l1_loss / huber_loss; all symmetric in their two arguments).
+ * term_k = factor_k * sum_k [/ count_k], applied in double; loss_out = double[1 + npairs] = total, per-term; the gradient
+ * is masked by s > 0 when relu_mask.  `numel` counts the elements of the BUFFER (NHWC, padded channels included; they are
+ * zero in both operands and contribute nothing), `count` is the LOGICAL N*C*H*W a mean divides by.  scratch:
+ * hnd_mse_scratch_elems() doubles (HND_OP_MSE).  Runs are bit-reproducible; kind = MSE with count = 0 gives the bits of
+ * hnd_mse_sum_fwd_bwd.  HND_ERR_INVALID before any launch: null pointers, npairs outside 1..8, numel not a positive
+ * multiple of 4, unknown kind, param negative or not finite, count outside 0..numel, or factor / count / param whose
+ * gradient weight (w / beta, w * delta) has no finite fp32 value.  A beta below FLT_MIN (0 included) is L1.  delta = 0 is
+ * accepted here (the loss is identically 0); torch's rule delta > 0 is enforced by the Python criterion HipHuberLoss. */
+typedef enum hnd_mimic_kind {
+  HND_MIMIC_MSE = 0,
+  HND_MIMIC_L1 = 1,
+  HND_MIMIC_SMOOTH_L1 = 2,
+  HND_MIMIC_HUBER = 3
+} hnd_mimic_kind;
+typedef struct hnd_mimic_pair {
+  const float* teacher;
+  const float* student;
+  float* grad;            /* may be NULL */
+  int64_t numel;          /* elements of the buffer, a positive multiple of 4 */
+  int64_t count;          /* divisor of a mean-reduced term (1..numel); 0 = sum reduction */
+  float factor;
+  float param;            /* beta (SMOOTH_L1) / delta (HUBER), finite and >= 0; ignored by MSE / L1 */
+  int32_t kind;           /* hnd_mimic_kind */
+  int32_t relu_mask;
+} hnd_mimic_pair;
+int hnd_mimic_loss_fwd_bwd(const hnd_mimic_pair* pairs, int npairs, double* loss_out, double* scratch, void* stream);
 /* grad *= *scale_dev unless *scale_dev == 1 (autograd's grad_output of the scalar loss) */
 int hnd_scale_by_device_scalar(float* x, int64_t numel, const float* scale_dev, void* stream);
 

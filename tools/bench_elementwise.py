@@ -3,6 +3,8 @@
 elementwise op moving the same bytes (what a plain streaming kernel reaches on this box).
 
 usage (GPU box):  python3 tools/bench_elementwise.py [--reps 30]
+                  python3 tools/bench_elementwise.py --mimic-kinds [--rounds 9] [--out profiles/mimic_loss_kinds.txt]
+                  (the loss launch per criterion kind beside MseLaunch, on the four maps of the default step)
 """
 import argparse
 import os
@@ -26,11 +28,69 @@ def timed(fn, reps):
     return a.elapsed_time(b) / reps
 
 
+def mimic_kinds(a, out_path=None):
+    """The loss launch of the default step (layer1..4 maps of batch 16, 3x800x1333; gradient written, layer4 masked by its
+    ReLU) through ops.MseLaunch and through ops.MimicLaunch for every kind, sum and mean.  `rounds` repeats, the variants
+    interleaved inside each; a repeat is the mean of `reps` launches between two HIP events.  A kind is judged against the
+    MseLaunch median plus that run's own spread of MseLaunch (max - min of its repeats)."""
+    from hnd_ghnd_object_detectors_amd import ops
+    dev = torch.device('cuda:0')
+    n = a.batch
+    g = torch.Generator(device=dev).manual_seed(1)
+    shapes = [(n, 200, 336, 256), (n, 100, 168, 512), (n, 50, 84, 1024), (n, 25, 42, 2048)]
+    maps = []
+    for i, shp in enumerate(shapes):        # ReLU outputs on both sides: exact zeros, and |d| on both sides of beta / delta
+        t = torch.randn(shp, device=dev, generator=g).clamp_(min=0)
+        s = torch.randn(shp, device=dev, generator=g).clamp_(min=0)
+        maps.append((t, s, torch.empty(shp, device=dev), 1.0, i == 3))
+    nbytes = sum(12 * t.numel() for t, *_ in maps)
+    variants = [('MseLaunch (hnd_mse_sum_fwd_bwd)', ops.MseLaunch(maps, dev))]
+    for kind, param in (('mse', 0.0), ('l1', 0.0), ('smooth_l1', 0.5), ('huber', 0.5)):
+        for red in ('sum', 'mean'):
+            pairs = [p + (kind, param, p[0].numel() if red == 'mean' else 0) for p in maps]
+            variants.append(('MimicLaunch %s %s' % (kind, red), ops.MimicLaunch(pairs, dev)))
+    for _, launch in variants:
+        for _ in range(3):
+            launch.run()
+    torch.cuda.synchronize()
+    times = [[] for _ in variants]
+    for _ in range(a.rounds):
+        for i, (_, launch) in enumerate(variants):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                launch.run()
+            e1.record()
+            e1.synchronize()
+            times[i].append(e0.elapsed_time(e1) / a.reps)
+    ops.sync_check()
+    med = [sorted(t)[len(t) // 2] for t in times]
+    spread = max(times[0]) - min(times[0])
+    lines = ['loss launch on the four maps of the default step (batch %d, %.2f GB moved), %d rounds x %d launches, interleaved'
+             % (n, nbytes / 1e9, a.rounds, a.reps),
+             '%-34s %9s %9s %9s %8s  %s' % ('launch', 'median ms', 'min ms', 'max ms', 'TB/s', 'vs MseLaunch median + spread')]
+    for (name, _), t, m in zip(variants, times, med):
+        verdict = '' if t is times[0] else ('within' if m <= med[0] + spread else 'SLOWER by %.4f ms' % (m - med[0] - spread))
+        lines.append('%-34s %9.4f %9.4f %9.4f %8.3f  %s' % (name, m, min(t), max(t), nbytes / m / 1e9, verdict))
+    lines.append('spread of MseLaunch (max - min of its %d repeats): %.4f ms' % (a.rounds, spread))
+    text = '\n'.join(lines)
+    print(text, flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, 'w') as f:
+            f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--batch', type=int, default=16)
+    ap.add_argument('--mimic-kinds', action='store_true', help='only the loss launch, per criterion kind, beside MseLaunch')
+    ap.add_argument('--rounds', type=int, default=7, help='--mimic-kinds: interleaved repeats of every variant')
+    ap.add_argument('--out', help='--mimic-kinds: also write the table to this file')
     a = ap.parse_args()
+    if a.mimic_kinds:
+        return mimic_kinds(a, a.out)
     from hnd_ghnd_object_detectors_amd import ops
     dev = torch.device('cuda:0')
     n = a.batch
