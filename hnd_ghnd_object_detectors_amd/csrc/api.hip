@@ -1,5 +1,8 @@
 // Error reporting and misc entry points of libhnd_hip.so.
+#include <atomic>
+
 #include "common.h"
+#include "stream_k_relay.h"
 
 #include <string.h>
 
@@ -14,13 +17,23 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 
-int relay_timeouts(int reset);     // conv_bstream.hip
-
 int check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) return HND_OK;
   set_error("%s: launch failed: %s", what, hipGetErrorString(e));
   return HND_ERR_LAUNCH;
+}
+
+int cu_count() {
+  static std::atomic<int> cached{0};
+  int v = cached.load(std::memory_order_relaxed);
+  if (v == 0) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    cached.store(v, std::memory_order_relaxed);
+  }
+  return v;
 }
 
 }  // namespace hnd

@@ -6,15 +6,30 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "hnd_hip.h"
 
 namespace hnd {
 
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);   // hipGetLastError -> status
+int cu_count();                       // compute units of the current device (cached; 256 when the query fails)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant
+// (register-array subscripts, inline-asm immediates)
+template <int N, class F, int... I>
+__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
+  (f(std::integral_constant<int, I>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+  static_for_impl<N>(f, std::make_integer_sequence<int, N>{});
+}
 
 // floor(x / d) for 0 <= x < 2^31 with a precomputed multiplier (d >= 1)
 struct FastDiv {

@@ -30,9 +30,6 @@
 
 #include <stdlib.h>
 
-#include <type_traits>
-#include <utility>
-
 namespace {
 
 using hnd::f32x4;
@@ -249,15 +246,6 @@ __global__ void __launch_bounds__(512, 1) bres_kernel(const hnd_conv_desc d, con
 //     memory operations retire in issue order, so "at most 28 outstanding" implies the slot has landed; stores or
 //     compiler-issued loads in between only make the wait stronger.  (Audit: tools/audit_bres_asm.py checks in the
 //     disassembly that no instruction touches a ring register between its load and the wait that names it.)
-template <int N, class F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  static_for_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
-
 // ACC = the slot lives in the accumulator half of the register file ("a": VMEM can target it and an MFMA reads its A
 // operand from it).  Half of the ring's slots do: with all 128 ring registers in architectural VGPRs hipcc ran out of
 // those and shuffled just-requested ring registers into AGPRs (copies of data that had not landed yet); with all of
@@ -359,9 +347,9 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
       f32x4 ring[RING][MI];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) aptr[mi] = a_ptr(cc * 64 + mi * 16 + l16);
-      static_for<RING>([&](auto U) __attribute__((always_inline)) {
+      hnd::static_for<RING>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value;
-        static_for<MI>([&](auto I) __attribute__((always_inline)) {
+        hnd::static_for<MI>([&](auto I) __attribute__((always_inline)) {
           ring_load<u * 64, (u & 1) != 0>(ring[u][decltype(I)::value], aptr[decltype(I)::value]);
         });
       });
@@ -392,12 +380,12 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
           ps = *(const f32x4*)(pro + g4 * 4);
           pb = *(const f32x4*)(pro + K + g4 * 4);
         }
-        static_for<KG>([&](auto G) __attribute__((always_inline)) {
+        hnd::static_for<KG>([&](auto G) __attribute__((always_inline)) {
           constexpr int g = decltype(G)::value, slot = g % RING;
           constexpr int kn = g + 1 < KG ? g + 1 : 0;
           const int bo = (kn & ~3) * 16 + bsw[kn & 3];
           ring_wait<4 * (RING - 1), (slot & 1) != 0>(ring[slot][0], ring[slot][1], ring[slot][2], ring[slot][3]);
-          static_for<MI>([&](auto MIc) __attribute__((always_inline)) {
+          hnd::static_for<MI>([&](auto MIc) __attribute__((always_inline)) {
             constexpr int mi = decltype(MIc)::value;
             f32x4 av = ring[slot][mi];
             if (PRO) {
@@ -507,18 +495,6 @@ int bres_kmax() {
   return e ? atoi(e) : 512;
 }
 
-int cu_count() {
-  static std::atomic<int> cached{0};
-  int v = cached.load(std::memory_order_relaxed);
-  if (v == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cached.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-
 template <int WN, int KQ, bool PRO>
 int launch_bres_t(const hnd_conv_desc& d, const BresArgs& a, size_t lds, int grid, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_set{0};
@@ -587,7 +563,7 @@ int bres_variant(const hnd_conv_desc& d) {
   if (wn == 2 ? (d.kdim != 64 && d.kdim != 128 && d.kdim != 256) : (d.kdim != 256 && d.kdim != 512)) return 0;
   const int bn = 64 * wn;
   if (d.cout % bn != 0) return 0;
-  const int per_xcd = cu_count() / 8, nsl = d.cout / bn;
+  const int per_xcd = hnd::cu_count() / 8, nsl = d.cout / bn;
   if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return 0;
   if ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_) return 0;
   const long long M = (long long)d.n * d.oh * d.ow;
@@ -637,7 +613,7 @@ int launch_bres(const hnd_conv_desc& d, hipStream_t stream) {
   a.cpg = d.w_group_rows / 64;
   const bool pro = d.pro_scale != nullptr;
   const size_t lds = ((size_t)64 * wn * d.kdim + (pro ? 2 * (size_t)d.kdim : 0) + 8 * 256) * sizeof(float);
-  const int grid = (cu_count() / 8) * 8;
+  const int grid = (hnd::cu_count() / 8) * 8;
   if (v2) {
     if (wn == 2) return d.kdim == 128 ? launch_bres2_p<2, 2>(d, a, lds, grid, stream)
                                       : launch_bres2_p<2, 4>(d, a, lds, grid, stream);

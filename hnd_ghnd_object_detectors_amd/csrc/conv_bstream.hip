@@ -28,16 +28,15 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "stream_k_relay.h"
 
 #include <stdlib.h>
-
-#include <type_traits>
-#include <utility>
 
 namespace {
 
 using hnd::f32x4;
 using hnd::FastDiv;
+using hnd::static_for;
 
 __device__ float g_zero_page[256];     // source of out-of-range taps: 8 k groups x 64 B + 64 B (zero-initialised)
 
@@ -50,15 +49,6 @@ struct BstreamArgs {
   float* relay;               // stream-K relay workspace (hnd_conv2d_igemm_workspace), or null: tiles round-robin
   int* err;                   // host-visible sticky error word (pinned, mapped): a relay wait that timed out raises it
 };
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void sfor(F&& f) {
-  sfor_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
 
 // ACC: the register lives in the accumulator half of the file (see conv_bres.hip: half of the ring does)
 template <int OFF, bool ACC>
@@ -80,17 +70,7 @@ __device__ __forceinline__ void slot_wait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4
 }
 
 // WN = wave columns: block tile (64 * 4 / WN) x (64 * WN), every wave a 64 x 64 tile of 4 x 4 MFMA tiles.
-//
-// Work split ("relay", a stream-K that keeps the accumulation order): the launch is T tiles x kg8 iterations of 128 k;
-// workgroup w (numbered so that one XCD holds consecutive w) takes the units [U w / G, U (w+1) / G) of that linear
-// space, so every CU gets the same number of MFMAs whatever T is -- no partial last round (M = 16 800 / 67 200 pixels
-// at layer4 / layer3: 528 or 1050 tiles on 256 CUs lost 31 % / 18 % to it).  A range that ends inside a tile computes
-// the tile's HEAD k range and parks the 128 x 128 accumulators in the workspace (64 KB per workgroup); the next
-// workgroup, whose range starts inside that tile, loads them and CONTINUES the same k chain before the epilogue --
-// the sum is the sequential one, bit for bit.  Order inside a workgroup: head first, whole tiles, tail last; with at
-// least one tile of work per workgroup (the host checks) the head of w-1 is finished before the tail of w starts, so
-// the flag wait never spins in practice and cannot deadlock (the writer waits for nobody).  Without a workspace the
-// tiles go round-robin (no relay).
+// Work split: the stream-K relay (stream_k_relay.h).
 template <int WN, bool PRO, bool TAPS>
 __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, const BstreamArgs a) {
   constexpr int WM = 4 / WN, BM = 64 * WM, BN = 64 * WN, MI = 4, NI = 4, NB = BN / 64, NST = 3;
@@ -117,26 +97,10 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
   enum { FULL = 0, HEAD = 1, TAIL = 2 };
   int nseg, first_full = 0, nfull = 0, tA = 0, offA = 0, tB = 0, offB = 0;
   bool has_head = false;
-  if (a.relay) {
-    const long long U = (long long)T * kg8;
-    const long long u0 = U * lb / G, u1 = U * (lb + 1) / G;
-    tA = (int)(u0 / kg8); offA = (int)(u0 - (long long)tA * kg8);
-    tB = (int)(u1 / kg8); offB = (int)(u1 - (long long)tB * kg8);
-    has_head = offB > 0;
-    first_full = tA + (offA > 0 ? 1 : 0);
-    nfull = tB - first_full;
-    nseg = (has_head ? 1 : 0) + nfull + (offA > 0 ? 1 : 0);
-  } else {
-    if (lb >= T) return;
-    nfull = nseg = (T - lb + G - 1) / G;                // tiles lb, lb + G, ...
-  }
-  // ---- relay bookkeeping behind the accumulator sets: [G] flags, launch counter, finished-workgroup ticket.
-  // A flag carries the EPOCH of the launch that raised it (counter + 1), never 0 / 1: a reader waits for exactly this
-  // launch's value and nobody resets anything, so a writer that arrives after its reader gave up (see the timeout
-  // below) cannot leave a flag that a later launch on this workspace would mistake for its own.  The counter is advanced
-  // by the last workgroup to finish; every workgroup reads it before it takes its ticket, so all G see one value.
+  if (!hnd::relay_split(a.relay, lb, G, T, kg8, nseg, first_full, nfull, tA, offA, tB, offB, has_head)) return;
+  // ---- relay bookkeeping behind the accumulator sets (stream_k_relay.h): flags, launch counter, ticket
   float* relay_p = a.relay;                             // [G][16][256] float4 accumulator sets
-  int* relay_f = (int*)(a.relay + (size_t)G * 16384);   // [G] flags, [G] = launch counter, [G + 1] = ticket
+  int* relay_f = (int*)(a.relay + (size_t)G * hnd::RELAY_SET);   // [G] flags, [G] = launch counter, [G + 1] = ticket
   int epoch = 0;                                        // (thread 0 only)
   if (a.relay && tid == 0) epoch = __hip_atomic_load(relay_f + G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
   auto launch_done = [&]() {
@@ -276,7 +240,7 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
     a_addr(ra, pa.it * 128, lp, okb);
     const float* bl0 = bt + (size_t)(2 * pb.it) * 64;
     const float* bl1 = bl0 + 64;
-    sfor<8>([&](auto U) __attribute__((always_inline)) {
+    static_for<8>([&](auto U) __attribute__((always_inline)) {
       constexpr int u = decltype(U)::value, u4 = u & 3;
       constexpr bool acc = (u & 1) != 0;
       const float* bl = u < 4 ? bl0 : bl1;
@@ -321,29 +285,7 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
       __builtin_amdgcn_wave_barrier();
     }
     if (kind == TAIL) {
-      // the head of this tile: accumulators parked by workgroup lb - 1 (which computed them FIRST, see above)
-      if (tid == 0) {
-        // Bounded (~2 s): the head was computed FIRST by its workgroup, so this does not spin in practice.  Should the
-        // flag never come (a workspace that was not zero-filled once, a neighbour that faulted or was starved) the
-        // launch must neither hang the GPU nor pass for correct: the wait gives up, raises the host-visible sticky
-        // error word -- every later hnd_conv2d_igemm / hnd_sync_check then fails with HND_ERR_LAUNCH / HND_ERR_ASYNC --
-        // and this tile's output is garbage by declaration.  Nothing is reset here (epoch flags, see above).
-        int spin = 0;
-        while (__hip_atomic_load(relay_f + (lb - 1), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-          if (++spin >= a.spin_limit) {
-            if (a.err) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      const f32x4* src = (const f32x4*)(relay_p + (size_t)(lb - 1) * 16384) + tid;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_nontemporal_load(src + (mi * NI + ni) * 256);
+      hnd::relay_load_head(relay_p, relay_f, lb, epoch, a, acc, tid);
     } else {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
@@ -364,7 +306,7 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
         ps = *(const f32x4*)(pro + cbase + g4 * 4);
         pb_ = *(const f32x4*)(pro + d.cin + cbase + g4 * 4);
       }
-      sfor<8>([&](auto U) __attribute__((always_inline)) {
+      static_for<8>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value, u4 = u & 3;
         constexpr bool sacc = (u & 1) != 0;
         const float* bl = u < 4 ? bl0 : bl1;
@@ -376,7 +318,7 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
         // the next k group's B fragments: the same stage, or chunk 0 of the next one
         const int rnext = u4 == 3 ? (rbuf + 1) % NST : rbuf;
         const float* Bn = Bs + rnext * STG + frow + bsw[(u4 + 1) & 3];
-        sfor<MI>([&](auto MIc) __attribute__((always_inline)) {
+        static_for<MI>([&](auto MIc) __attribute__((always_inline)) {
           constexpr int mi = decltype(MIc)::value;
           f32x4 av = ring[u][mi];
           if (PRO) {
@@ -418,15 +360,7 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
     }
 
     if (kind == HEAD) {
-      // park the accumulators for workgroup lb + 1 and raise the flag; no epilogue
-      f32x4* dst = (f32x4*)(relay_p + (size_t)lb * 16384) + tid;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) __builtin_nontemporal_store(acc[mi][ni], dst + (mi * NI + ni) * 256);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (tid == 0 && a.dbg != 2) __hip_atomic_store(relay_f + lb, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      hnd::relay_park_head(relay_p, relay_f, lb, epoch, [&] { return a.dbg != 2; }, acc, tid);      // no epilogue
     } else {
       // ---- epilogue of this tile; the loads of the next segment are already in flight
       const int col0 = nt * BN + wn * 64 + l16 * 4;     // hnd::chan_of_row of the wave's packed rows
@@ -444,18 +378,6 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the stream's last (unused) prefetches land before the end
   launch_done();
-}
-
-int cu_count_() {
-  static std::atomic<int> cached{0};
-  int v = cached.load(std::memory_order_relaxed);
-  if (v == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cached.store(v, std::memory_order_relaxed);
-  }
-  return v;
 }
 
 // The sticky error word: one int of pinned, device-mapped host memory per process.  A kernel raises it with a
@@ -522,15 +444,6 @@ int launch_w(const hnd_conv_desc& d, const BstreamArgs& a, size_t lds, int grid,
 
 namespace hnd {
 
-// tiles of the launch and the persistent grid
-static void bstream_grid(const hnd_conv_desc& d, int wn, int& mtiles, int& ntiles, int& grid) {
-  const long long M = (long long)d.n * d.oh * d.ow;
-  const int bm = 64 * (4 / wn), bn = 64 * wn;
-  mtiles = (int)((M + bm - 1) / bm);
-  ntiles = d.cout / bn;
-  grid = (cu_count_() / 8) * 8;
-}
-
 // 0 = not taken, 1 = 256 x 64 block tile (one wave column), 2 = 128 x 128 (two)
 int bstream_variant(const hnd_conv_desc& d) {
   const char* e = getenv("HND_BSTREAM");                // 0 = off (A/B)
@@ -567,26 +480,24 @@ int bstream_variant(const hnd_conv_desc& d) {
   // ... and only with at least one tile per workgroup (the relay's condition): a persistent kernel that leaves CUs
   // idle loses to the tiled kernel's small blocks (validation at batch 1: 148 -> 128 img/s when it took those too)
   int mtiles, ntiles, grid;
-  bstream_grid(d, wn, mtiles, ntiles, grid);
+  relay_grid(d, wn, mtiles, ntiles, grid);
   if ((long long)mtiles * ntiles < grid) return 0;
   return wn;
 }
 
-// the relay needs at least one whole tile of work per workgroup (see the kernel)
-size_t bstream_workspace(const hnd_conv_desc& d) {
-  const int wn = bstream_variant(d);
-  if (wn == 0) return 0;
-  int mtiles, ntiles, grid;
-  bstream_grid(d, wn, mtiles, ntiles, grid);
-  if ((long long)mtiles * ntiles < grid) return 0;
-  return (size_t)grid * (16384 * sizeof(float) + sizeof(int)) + 16 * sizeof(int);     // sets, flags, counter + ticket
-}
+size_t bstream_workspace(const hnd_conv_desc& d) { return relay_workspace(d, bstream_variant(d)); }
 
-// the same sticky error word for the emulated B-streamed kernel (conv_bxs.hip)
-int* relay_err_host() { return relay_error_word(); }
-int* relay_err_dev() {
-  (void)relay_error_word();
-  return g_err_dev;
+// (stream_k_relay.h) one sticky error word for both B-streamed kernels
+int relay_launch_check(const char* kernel, int& spin_limit, int*& err) {
+  if (__atomic_load_n(relay_error_word(), __ATOMIC_RELAXED) != 0) {
+    set_error("hnd_conv2d_igemm(%s): an earlier launch gave up waiting for a neighbour's partial tile (relay "
+              "time-out): results since then are invalid; hnd_relay_timeouts(1) acknowledges", kernel);
+    return HND_ERR_LAUNCH;
+  }
+  err = g_err_dev;
+  spin_limit = 1 << 21;
+  if (const char* e = getenv("HND_BSTREAM_SPIN")) spin_limit = atoi(e) > 0 ? atoi(e) : spin_limit;
+  return HND_OK;
 }
 
 int relay_timeouts(int reset) {
@@ -606,18 +517,10 @@ int launch_bstream(const hnd_conv_desc& d, hipStream_t stream) {
   const int bn = 64 * wn;
   BstreamArgs a;
   int grid;
-  const int* errw = relay_error_word();
-  if (__atomic_load_n(errw, __ATOMIC_RELAXED) != 0) {
-    set_error("hnd_conv2d_igemm(bstream): an earlier launch gave up waiting for a neighbour's partial tile (relay "
-              "time-out): results since then are invalid; hnd_relay_timeouts(1) acknowledges");
-    return HND_ERR_LAUNCH;
-  }
-  a.err = g_err_dev;
-  a.spin_limit = 1 << 21;
-  if (const char* e = getenv("HND_BSTREAM_SPIN")) a.spin_limit = atoi(e) > 0 ? atoi(e) : a.spin_limit;
+  if (const int rc = relay_launch_check("bstream", a.spin_limit, a.err)) return rc;
   a.div_ow = make_fastdiv((unsigned)d.ow);
   a.div_oh = make_fastdiv((unsigned)d.oh);
-  bstream_grid(d, wn, a.mtiles, a.ntiles, grid);
+  relay_grid(d, wn, a.mtiles, a.ntiles, grid);
   a.kg8 = d.kdim / 128;
   a.dbg = getenv("HND_BSTREAM_DBG") ? atoi(getenv("HND_BSTREAM_DBG")) : 0;
   a.relay = (d.relay_ws && bstream_workspace(d) > 0) ? d.relay_ws : nullptr;

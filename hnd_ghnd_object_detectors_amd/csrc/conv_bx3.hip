@@ -23,19 +23,20 @@
 // at K = N = 256 the operands' 4 M (K + N) bytes bound a launch at 0.35 ms of HBM time against 0.34 ms of matrix time.
 #include <atomic>
 
+#include "bf16x3.h"
 #include "common.h"
 
 #include <stdlib.h>
 
-#include <type_traits>
-#include <utility>
-
 namespace {
 
+using hnd::bf8;
+using hnd::cu_count;
 using hnd::f32x4;
 using hnd::FastDiv;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+using hnd::split_pair;
+using hnd::static_for;
+using hnd::u32x4;
 
 struct Bx3Args {
   FastDiv div_ow, div_oh;     // m -> (n, oh, ow) of the A rows
@@ -47,15 +48,6 @@ struct Bx3Args {
   int cpg;                    // chunks per weight group (Winograd component), 0 = one group
   int res_up;                 // RES: res1 is the exactly 2x coarser map, nearest-upsampled (the FPN's top-down path)
 };
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void xfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void xfor(F&& f) {
-  xfor_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
 
 // All ring slots live in the accumulator half of the register file (VMEM can target it; the vector ALU reaches it through
 // v_accvgpr_read): with ring registers among the architectural ones hipcc sat at its limit and moved just-requested
@@ -90,17 +82,6 @@ template <int CNT>
 __device__ __forceinline__ void rwait8(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4, f32x4& a5, f32x4& a6,
                                        f32x4& a7) {
   rwait<CNT>(a0, a1, a2, a3, a4, a5, a6, a7);
-}
-
-__device__ __forceinline__ void split_pair(float x0, float x1, uint32_t& hp, uint32_t& mp, uint32_t& lp) {
-  const uint32_t a0 = __float_as_uint(x0), a1 = __float_as_uint(x1);
-  const uint32_t h0 = a0 & 0xffff0000u, h1 = a1 & 0xffff0000u;
-  const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-  const uint32_t m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-  const float q0 = r0 - __uint_as_float(m0), q1 = r1 - __uint_as_float(m1);
-  hp = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-  mp = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-  lp = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
 }
 
 // KS = K / 32 (4: K = 128, 8: K = 256).  Block = 4 waves, one 64-row chunk each at a time, all on the workgroup's 64 columns.
@@ -177,9 +158,9 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
       f32x4 ring[RING][MI][2];
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) aptr[mi] = a_ptr(cc, mi);
-      xfor<RING>([&](auto U) __attribute__((always_inline)) {
+      static_for<RING>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value;
-        xfor<MI>([&](auto I) __attribute__((always_inline)) {
+        static_for<MI>([&](auto I) __attribute__((always_inline)) {
           constexpr int mi = decltype(I)::value;
           // (KS == RING: every k step of the first tile is requested here)
           rload<(u % KS) * 128>(ring[u][mi][0], aptr[mi]);
@@ -222,7 +203,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
         const float* nptr[MI];
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) nptr[mi] = a_ptr(cn, mi);
-        xfor<KS>([&](auto G) __attribute__((always_inline)) {
+        static_for<KS>([&](auto G) __attribute__((always_inline)) {
           constexpr int ks = decltype(G)::value, slot = ks % RING, par = ks & 1;
           constexpr int slot1 = (ks + 1) % RING;            // the step whose planes are made during this one
           if constexpr (MK && ks == KS - 4) {
@@ -255,7 +236,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
             }
           }
           // slot `slot` was split during the previous step: refill it for the step RING ahead (this tile or the next)
-          xfor<MI>([&](auto I) __attribute__((always_inline)) {
+          static_for<MI>([&](auto I) __attribute__((always_inline)) {
             constexpr int mi = decltype(I)::value;
             if constexpr (ks + RING < KS) {
               rload<(ks + RING) * 128>(ring[slot][mi][0], aptr[mi]);
@@ -281,7 +262,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
           const int pos = ((ks * 4 + g4) ^ l16) * 8;
           bf8 bcur[3], bnxt[3];
           bcur[0] = bfirst[0]; bcur[1] = bfirst[1]; bcur[2] = bfirst[2];
-          xfor<NI>([&](auto NIc) __attribute__((always_inline)) {
+          static_for<NI>([&](auto NIc) __attribute__((always_inline)) {
             constexpr int ni = decltype(NIc)::value;
             if constexpr (ni + 1 < NI) {
               const uint16_t* br = Bs + ((ni + 1) * 16 + l16) * K + pos;
@@ -290,7 +271,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
               const uint16_t* br = Bs + l16 * K + ((((ks + 1) % KS) * 4 + g4) ^ l16) * 8;
               bfirst[0] = *(const bf8*)(br); bfirst[1] = *(const bf8*)(br + PLANE); bfirst[2] = *(const bf8*)(br + 2 * PLANE);
             }
-            xfor<MI>([&](auto MIc) __attribute__((always_inline)) {
+            static_for<MI>([&](auto MIc) __attribute__((always_inline)) {
               constexpr int mi = decltype(MIc)::value;
               auto frag = [&](int q) __attribute__((always_inline)) {
                 const u32x4 t = {pl[par][q][mi][0], pl[par][q][mi][1], pl[par][q][mi][2], pl[par][q][mi][3]};
@@ -391,18 +372,6 @@ __global__ void pack_bx3_kernel(const float* __restrict__ w, uint16_t* __restric
   }
 }
 
-int cu_count_bx3() {
-  static std::atomic<int> cached{0};
-  int v = cached.load(std::memory_order_relaxed);
-  if (v == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cached.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-
 template <int KS, bool RES, bool MO, bool MK = false>
 int launch_bx3_t(const hnd_conv_desc& d, const Bx3Args& a, int grid, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_set{0};
@@ -437,7 +406,7 @@ static bool bx3_recommended(long long rows_per_image, int kdim, int cout) {
   if (kdim != 128 && (kdim % 256 != 0 || kdim > 2048)) return false;
   // (round 6 A/B, same box, img/s at batch 16 / batch 4: K >= 1024 launches on the B-streamed build instead 214.2 / 170.7,
   // K >= 512 210.5 / 161.2, as shipped 216.2 / 176.6 -- the passes over k stay)
-  const int per_xcd = cu_count_bx3() / 8, nsl = cout / 64;
+  const int per_xcd = cu_count() / 8, nsl = cout / 64;
   if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return false;
   const long long nteams = 8ll * (per_xcd / nsl);
   const long long chunks_at_16 = (rows_per_image * 16 + 63) / 64;
@@ -461,7 +430,7 @@ bool bx3_applies(const hnd_conv_desc& d) {
   // a residual of y's geometry, or the exactly 2x coarser map of the FPN's top-down path (whole 4-pixel groups per row)
   if (d.res1 && d.res1_mode == 1 && (d.yh != 2 * d.res1_h || d.yw != 2 * d.res1_w || d.ow % 4 != 0)) return false;
   if (d.cout % 64 != 0 || d.ldc % 4 != 0 || ((uintptr_t)d.y % 16) != 0) return false;
-  const int per_xcd = cu_count_bx3() / 8, nsl = d.cout / 64;
+  const int per_xcd = cu_count() / 8, nsl = d.cout / 64;
   if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return false;
   if (d.y_sh != 1 || d.y_sw != 1 || d.y_oh != 0 || d.y_ow != 0 || d.yh != d.oh || d.yw != d.ow) return false;
   if ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_) return false;
@@ -480,7 +449,7 @@ static int launch_bx3_one(const hnd_conv_desc& d, int kpart, hipStream_t stream)
   a.nchunks = (a.mrows + 63) / 64;
   a.cpg = d.w_group_rows / 64;
   a.res_up = d.res1 && d.res1_mode == 1;
-  const int grid = (cu_count_bx3() / 8) * 8;
+  const int grid = (cu_count() / 8) * 8;
   if (d.mask_bits)      // (with a residual of y's geometry and no mask_out: bx3_applies)
     return kpart == 128 ? launch_bx3_t<4, true, false, true>(d, a, grid, stream)
                         : launch_bx3_t<8, true, false, true>(d, a, grid, stream);
@@ -520,7 +489,7 @@ static const int BX3_TILED_128_ROWS_FROM = 10;
 static int bx3_pick(const hnd_conv_desc& d) {
   if (!bx3_applies(d)) return 0;
   const long long M = (long long)d.n * d.oh * d.ow, chunks = (M + 63) / 64;
-  const long long nteams = 8ll * ((cu_count_bx3() / 8) / (d.cout / 64));
+  const long long nteams = 8ll * ((cu_count() / 8) / (d.cout / 64));
   const long long per_team = (chunks + nteams - 1) / nteams;
   const bool is_long = d.kdim >= 1024;
   const int rows = is_long && per_team >= BX3_TILED_128_ROWS_FROM ? 2 : 1;

@@ -4,7 +4,7 @@
 // is hidden by occupancy instead of a hand-counted register ring.  Everything here is compiler-visible loads + LDS.
 //
 // SAME BITS as bx3_kernel (DESIGN section 4 rule 4) -- what that rests on:
-//   * operands split by truncation exactly as split_pair / pack_bx3_kernel (the weight image is the persistent build's own);
+//   * operands split by the family's one split_pair (bf16x3.h; the weight image is the persistent build's own);
 //   * the same v_mfma_f32_16x16x32_bf16 with every k value in the lane and element position it has there: lane l16 = row (A) /
 //     column (B) of the 16-wide tile, lane group g4 holds k = 32 ks + 8 g4 .. + 7;
 //   * per 32-k step the six products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, k steps ascending, a fresh accumulator per
@@ -20,14 +20,15 @@
 // group g4 and the 8 of g4 + 1 that one ds_read_b128 lane group holds fall on all 64 banks once).  The B piece of the NEXT piece is requested before the
 // current piece's MFMAs, its A fragments as soon as the current ones are split.  Resource usage of both
 // instantiations: profiles/r07_bx3_tiled_resources.txt.
+#include "bf16x3.h"
 #include "common.h"
 
 namespace {
 
+using hnd::bf8;
 using hnd::f32x4;
 using hnd::FastDiv;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+using hnd::u32x4;
 
 struct Bx3tArgs {
   FastDiv div_ow, div_oh;     // m -> (n, oh, ow) of the A rows
@@ -38,18 +39,6 @@ struct Bx3tArgs {
   int ngroups;                // weight groups of the image
   int res_up;                 // res1 is the exactly 2x coarser map, nearest-upsampled
 };
-
-// (the persistent build's split, verbatim)
-__device__ __forceinline__ void split_pair_t(float x0, float x1, uint32_t& hp, uint32_t& mp, uint32_t& lp) {
-  const uint32_t a0 = __float_as_uint(x0), a1 = __float_as_uint(x1);
-  const uint32_t h0 = a0 & 0xffff0000u, h1 = a1 & 0xffff0000u;
-  const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-  const uint32_t m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-  const float q0 = r0 - __uint_as_float(m0), q1 = r1 - __uint_as_float(m1);
-  hp = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-  mp = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-  lp = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-}
 
 // MI: 16-row groups per wave; the workgroup's 4 waves stack to a 64 MI-row tile on one 64-column slice.
 template <int MI>
@@ -149,7 +138,7 @@ __global__ void __launch_bounds__(256, MI == 1 ? 3 : 2) bx3t_kernel(const hnd_co
           const f32x4 v = acur[mi][ksl][j >> 1];
           const float x0 = (j & 1) ? v.z : v.x, x1 = (j & 1) ? v.w : v.y;
           uint32_t hp, mp, lp;
-          split_pair_t(x0, x1, hp, mp, lp);
+          hnd::split_pair(x0, x1, hp, mp, lp);
           h[j] = hp; m[j] = mp; l[j] = lp;
         }
         ah[mi] = __builtin_bit_cast(bf8, h);

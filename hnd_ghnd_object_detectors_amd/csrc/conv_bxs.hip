@@ -14,7 +14,7 @@
 //   * the split of k step s + 1 into bf16 planes rides between the MFMAs of k step s (conv_bx3.hip);
 //     (measured and not kept, round 6: the stage's DMA pieces issued one per MFMA tile instead of at the top of the step --
 //     4 % slower; the next step's first B fragments read a step early -- nothing)
-//   * tiles 128 x 128 (two wave columns) or 256 x 64, every wave 64 x 64; the stream-K relay of conv_bstream.hip (a
+//   * tiles 128 x 128 (two wave columns) or 256 x 64, every wave 64 x 64; the stream-K relay (stream_k_relay.h: a
 //     workgroup whose share ends inside a tile parks the accumulators, its neighbour continues the same k chain) keeps
 //     every CU busy whatever the tile count; epilogue = conv_epilogue.h (any operand set, statistics, backward sums).
 // Counter note (vmcnt, in-order retire): per k step s = 4 i + u every lane issues, in this order, [u even: the NBL LDS-DMA
@@ -23,25 +23,20 @@
 // 32 + NBL.  Epilogue loads / stores between two tiles are younger still: they only make these waits stricter.
 #include <atomic>
 
+#include "bf16x3.h"
 #include "common.h"
 #include "conv_epilogue.h"
+#include "stream_k_relay.h"
 
 #include <stdlib.h>
 
-#include <type_traits>
-#include <utility>
-
-namespace hnd {
-int* relay_err_host();            // conv_bstream.hip: the process-wide sticky error word (host view)
-int* relay_err_dev();             // ... and its device view (nullptr when no pinned memory was to be had)
-}  // namespace hnd
-
 namespace {
 
+using hnd::bf8;
 using hnd::f32x4;
 using hnd::FastDiv;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
-typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+using hnd::static_for;
+using hnd::u32x4;
 
 __device__ float g_bxs_zero_page[128];     // source of out-of-range taps: a lane reads 2 x 16 B at g4 * 32 + {0, 128} B
 
@@ -54,15 +49,6 @@ struct BxsArgs {
   float* relay;               // stream-K relay workspace (hnd_conv2d_igemm_workspace), or null: tiles round-robin
   int* err;                   // host-visible sticky error word
 };
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void zfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void zfor(F&& f) {
-  zfor_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
 
 // ring slots live in the accumulator half of the register file (conv_bx3.hip)
 template <int OFF>
@@ -122,25 +108,13 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
   const int M = d.n * d.oh * d.ow;
   const int nit = a.nit;
 
-  // ---- this workgroup's segments: (tile, first iteration, end iteration, kind) -- conv_bstream.hip's relay
+  // ---- this workgroup's segments: (tile, first iteration, end iteration, kind)
   enum { FULL = 0, HEAD = 1, TAIL = 2 };
   int nseg, first_full = 0, nfull = 0, tA = 0, offA = 0, tB = 0, offB = 0;
   bool has_head = false;
-  if (a.relay) {
-    const long long U = (long long)T * nit;
-    const long long u0 = U * lb / G, u1 = U * (lb + 1) / G;
-    tA = (int)(u0 / nit); offA = (int)(u0 - (long long)tA * nit);
-    tB = (int)(u1 / nit); offB = (int)(u1 - (long long)tB * nit);
-    has_head = offB > 0;
-    first_full = tA + (offA > 0 ? 1 : 0);
-    nfull = tB - first_full;
-    nseg = (has_head ? 1 : 0) + nfull + (offA > 0 ? 1 : 0);
-  } else {
-    if (lb >= T) return;
-    nfull = nseg = (T - lb + G - 1) / G;                // tiles lb, lb + G, ...
-  }
+  if (!hnd::relay_split(a.relay, lb, G, T, nit, nseg, first_full, nfull, tA, offA, tB, offB, has_head)) return;
   float* relay_p = a.relay;                             // [G][16][256] float4 accumulator sets
-  int* relay_f = (int*)(a.relay + (size_t)G * 16384);   // [G] flags (launch epochs), [G] = launch counter, [G + 1] = ticket
+  int* relay_f = (int*)(a.relay + (size_t)G * hnd::RELAY_SET);   // [G] flags (launch epochs), [G] = launch counter, [G + 1] = ticket
   int epoch = 0;                                        // (thread 0 only)
   if (a.relay && tid == 0) epoch = __hip_atomic_load(relay_f + G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
   auto launch_done = [&]() {
@@ -273,10 +247,10 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
   f32x4 ring[4][MI][2];
   // ---- fill, in the steady state's issue order: B(0) A(0) A(1) B(1) A(2) A(3); BIG: B(0, 1) A(0) A(1) A(2) A(3)
   b_issue(bt, 2 * pn.it, 0);
-  zfor<4>([&](auto U) __attribute__((always_inline)) {
+  static_for<4>([&](auto U) __attribute__((always_inline)) {
     constexpr int u = decltype(U)::value, hf = u >> 1, o = (u & 1) * 128;
     if constexpr (u == 2 && !BIG) b_issue(bt, 2 * pn.it + 1, 1);
-    zfor<MI>([&](auto I) __attribute__((always_inline)) {
+    static_for<MI>([&](auto I) __attribute__((always_inline)) {
       constexpr int mi = decltype(I)::value;
       aload<o>(ring[u][mi][0], lpn[hf][mi]);
       aload<o + 16>(ring[u][mi][1], lpn[hf][mi]);
@@ -329,13 +303,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
       const f32x4 v = ring[0][mi][j >> 1];
       const bool ok = (okc[0] >> mi) & 1;
       const float x0 = pro_apply((j & 1) ? v.z : v.x, 2 * j, ok), x1 = pro_apply((j & 1) ? v.w : v.y, 2 * j + 1, ok);
-      const uint32_t h0 = __float_as_uint(x0) & 0xffff0000u, h1 = __float_as_uint(x1) & 0xffff0000u;
-      const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-      const uint32_t m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-      const float q0 = r0 - __uint_as_float(m0), q1 = r1 - __uint_as_float(m1);
-      pl[0][0][mi][j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-      pl[0][1][mi][j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-      pl[0][2][mi][j] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
+      hnd::split_pair(x0, x1, pl[0][0][mi][j], pl[0][1][mi][j], pl[0][2][mi][j]);
     }
 
   int rbuf = 0;                                         // LDS stage the MFMAs read; stage rbuf + 2 is being filled
@@ -365,25 +333,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
       __builtin_amdgcn_wave_barrier();
     }
     if (kind == TAIL) {
-      // the head of this tile: accumulators parked by workgroup lb - 1 (which computed them FIRST); bounded wait, a
-      // time-out raises the sticky host-visible error word (conv_bstream.hip, hnd_relay_timeouts)
-      if (tid == 0) {
-        int spin = 0;
-        while (__hip_atomic_load(relay_f + (lb - 1), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) != epoch) {
-          if (++spin >= a.spin_limit) {
-            if (a.err) __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            break;
-          }
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      const f32x4* src = (const f32x4*)(relay_p + (size_t)(lb - 1) * 16384) + tid;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) acc[mi][ni] = __builtin_nontemporal_load(src + (mi * NI + ni) * 256);
+      hnd::relay_load_head(relay_p, relay_f, lb, epoch, a, acc, tid);
     } else {
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
@@ -392,7 +342,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
     }
 
     for (int it = it0; it < it1; ++it) {
-      zfor<4>([&](auto U) __attribute__((always_inline)) {
+      static_for<4>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value, hf = u >> 1, par = u & 1, u1 = (u + 1) & 3;
         if constexpr (BIG ? (u == 0) : ((u & 1) == 0)) {
           // this lane's pieces of stage `rbuf` have landed (issued two stages / one iteration ago); then everybody's
@@ -402,7 +352,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
           b_issue(bt, 2 * pn.it + (BIG ? 0 : hf), wst);         // the same half (BIG: the whole) of the NEXT iteration
         }
         // slot u was split during the previous step: refill it with step u of the next iteration
-        zfor<MI>([&](auto I) __attribute__((always_inline)) {
+        static_for<MI>([&](auto I) __attribute__((always_inline)) {
           constexpr int mi = decltype(I)::value;
           aload<par * 128>(ring[u][mi][0], lpn[hf][mi]);
           aload<par * 128 + 16>(ring[u][mi][1], lpn[hf][mi]);
@@ -419,13 +369,13 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
         bcur[0] = *(const bf8*)(stage + pos);
         bcur[1] = *(const bf8*)(stage + PLANE + pos);
         bcur[2] = *(const bf8*)(stage + 2 * PLANE + pos);
-        zfor<NI>([&](auto NIc) __attribute__((always_inline)) {
+        static_for<NI>([&](auto NIc) __attribute__((always_inline)) {
           constexpr int ni = decltype(NIc)::value;
           if constexpr (ni + 1 < NI) {
             const uint16_t* br = stage + (ni + 1) * 16 * 64 + pos;
             bnxt[0] = *(const bf8*)(br); bnxt[1] = *(const bf8*)(br + PLANE); bnxt[2] = *(const bf8*)(br + 2 * PLANE);
           }
-          zfor<MI>([&](auto MIc) __attribute__((always_inline)) {
+          static_for<MI>([&](auto MIc) __attribute__((always_inline)) {
             constexpr int mi = decltype(MIc)::value;
             auto frag = [&](int q) __attribute__((always_inline)) {
               const u32x4 t = {pl[par][q][mi][0], pl[par][q][mi][1], pl[par][q][mi][2], pl[par][q][mi][3]};
@@ -479,15 +429,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
     }
 
     if (kind == HEAD) {
-      // park the accumulators for workgroup lb + 1 and raise the flag; no epilogue
-      f32x4* dst = (f32x4*)(relay_p + (size_t)lb * 16384) + tid;
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NI; ++ni) __builtin_nontemporal_store(acc[mi][ni], dst + (mi * NI + ni) * 256);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-      if (tid == 0) __hip_atomic_store(relay_f + lb, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+      hnd::relay_park_head(relay_p, relay_f, lb, epoch, [] { return true; }, acc, tid);      // no epilogue
     } else {
       // ---- epilogue of this tile; the loads of the next segment are already in flight
       const int col0 = nt * BN + wn * 64 + l16 * 4;     // hnd::chan_of_row of the wave's packed rows
@@ -555,18 +497,6 @@ __global__ void pack_bxs_kernel(const float* __restrict__ w, uint16_t* __restric
   }
 }
 
-int cu_count_bxs() {
-  static std::atomic<int> cached{0};
-  int v = cached.load(std::memory_order_relaxed);
-  if (v == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cached.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-
 template <int WN, bool PRO, bool TAPS>
 int launch_t(const hnd_conv_desc& d, const BxsArgs& a, size_t lds, int grid, hipStream_t stream) {
   static std::atomic<unsigned long long> attr_set{0};
@@ -603,14 +533,6 @@ size_t bxs_lds_bytes(const hnd_conv_desc& d, int wn) {
 
 namespace hnd {
 
-static void bxs_grid(const hnd_conv_desc& d, int wn, int& mtiles, int& ntiles, int& grid) {
-  const long long M = (long long)d.n * d.oh * d.ow;
-  const int bm = 64 * (4 / wn), bn = 64 * wn;
-  mtiles = (int)((M + bm - 1) / bm);
-  ntiles = d.cout / bn;
-  grid = (cu_count_bxs() / 8) * 8;
-}
-
 // 0 = not taken (no stream image attached, or a shape the kernel does not cover), 1 = 256 x 64 block tile, 2 = 128 x 128.
 // Attaching hnd_conv_desc.w_bf16x3s ASKS for the kernel (the host attaches it by LAYER: hnd_bf16x3s_recommended).
 int bxs_variant(const hnd_conv_desc& d) {
@@ -631,15 +553,7 @@ int bxs_variant(const hnd_conv_desc& d) {
   return wn;
 }
 
-// the relay needs at least one whole tile of work per workgroup (conv_bstream.hip)
-size_t bxs_workspace(const hnd_conv_desc& d) {
-  const int wn = bxs_variant(d);
-  if (wn == 0) return 0;
-  int mtiles, ntiles, grid;
-  bxs_grid(d, wn, mtiles, ntiles, grid);
-  if ((long long)mtiles * ntiles < grid) return 0;
-  return (size_t)grid * (16384 * sizeof(float) + sizeof(int)) + 16 * sizeof(int);     // sets, flags, counter + ticket
-}
+size_t bxs_workspace(const hnd_conv_desc& d) { return relay_workspace(d, bxs_variant(d)); }
 
 int launch_bxs(const hnd_conv_desc& d, hipStream_t stream) {
   const int wn = bxs_variant(d);
@@ -649,20 +563,12 @@ int launch_bxs(const hnd_conv_desc& d, hipStream_t stream) {
   }
   BxsArgs a;
   int grid;
-  const int* errw = relay_err_host();
-  if (__atomic_load_n(errw, __ATOMIC_RELAXED) != 0) {
-    set_error("hnd_conv2d_igemm(bxs): an earlier launch gave up waiting for a neighbour's partial tile (relay time-out): "
-              "results since then are invalid; hnd_relay_timeouts(1) acknowledges");
-    return HND_ERR_LAUNCH;
-  }
-  a.err = relay_err_dev();
-  a.spin_limit = 1 << 21;
-  if (const char* e = getenv("HND_BSTREAM_SPIN")) a.spin_limit = atoi(e) > 0 ? atoi(e) : a.spin_limit;
+  if (const int rc = relay_launch_check("bxs", a.spin_limit, a.err)) return rc;
   a.div_ow = make_fastdiv((unsigned)d.ow);
   a.div_oh = make_fastdiv((unsigned)d.oh);
   a.div_cin = make_fastdiv((unsigned)d.cin);
   a.div_kw = make_fastdiv((unsigned)d.kw);
-  bxs_grid(d, wn, a.mtiles, a.ntiles, grid);
+  relay_grid(d, wn, a.mtiles, a.ntiles, grid);
   a.nit = d.kdim / 128;
   a.relay = (d.relay_ws && bxs_workspace(d) > 0) ? d.relay_ws : nullptr;
   const size_t lds = bxs_lds_bytes(d, wn);

@@ -29,8 +29,6 @@
 #include <stdlib.h>
 
 #include <atomic>
-#include <type_traits>
-#include <utility>
 
 namespace {
 
@@ -49,15 +47,6 @@ struct WringArgs {
   int co_pad, ncols_pad;      // slab extent (wgrad_reduce_kernel's layout)
   int splits;
 };
-
-template <int N, class F, int... I>
-__device__ __forceinline__ void wfor_impl(F&& f, std::integer_sequence<int, I...>) {
-  (f(std::integral_constant<int, I>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void wfor(F&& f) {
-  wfor_impl<N>(f, std::make_integer_sequence<int, N>{});
-}
 
 template <int OFF>
 __device__ __forceinline__ void rload(f32x4& dst, const float* p) {
@@ -206,9 +195,9 @@ __global__ void __launch_bounds__(256, WPS) wgrad_ring_kernel(const WringArgs a)
     for (int j = 0; j < 4 * BH; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   if (nblk > 0) {
-    wfor<RING>([&](auto U) __attribute__((always_inline)) { issue(U); });
+    hnd::static_for<RING>([&](auto U) __attribute__((always_inline)) { issue(U); });
     for (int b = 0; b < nblk * (8 / RING); ++b) {            // a block = 8 k-steps = 8 / RING turns of the ring
-      wfor<RING>([&](auto U) __attribute__((always_inline)) {
+      hnd::static_for<RING>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value;
         if constexpr (NL == 2) rwait<VM>(ra[u][0], rb[u][0]);
         else if constexpr (NL == 3 && AH == 2) rwait<VM>(ra[u][0], ra[u][1], rb[u][0]);
@@ -265,18 +254,6 @@ __global__ void __launch_bounds__(256, WPS) wgrad_ring_kernel(const WringArgs a)
           *(f32x4*)(slab + (size_t)co * a.ncols_pad + col0 + 64 * hb + 4 * l16) = v;
         }
       }
-}
-
-int cu_count_wr() {
-  static std::atomic<int> cached{0};
-  int v = cached.load(std::memory_order_relaxed);
-  if (v == 0) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-    cached.store(v, std::memory_order_relaxed);
-  }
-  return v;
 }
 
 // The tap form (direct 2x2 convs; ~100 vector instructions of address arithmetic, prologue and padding selects per
@@ -358,7 +335,7 @@ static void wring_plan(const hnd_wgrad_desc& d, WringArgs& a, int& ah, int& bh) 
   const int groups = d.groups > 1 ? d.groups : 1;
   const int tiles = a.rtiles * a.ctiles * groups;
   // one workgroup per CU (two for the tap form), as many as divide evenly
-  int splits = d.splitk > 0 ? d.splitk : (cu_count_wr() * (small ? 2 : 1)) / tiles;
+  int splits = d.splitk > 0 ? d.splitk : (hnd::cu_count() * (small ? 2 : 1)) / tiles;
   if (splits < 1) splits = 1;
   if (splits > a.total_blocks) splits = a.total_blocks;
   if (splits > 512) splits = 512;

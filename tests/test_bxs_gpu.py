@@ -241,3 +241,48 @@ def test_bxs_randomised_shapes_without_bx3_images_against_the_native_kernel(ops)
     from tests.conftest import record_achieved
     record_achieved('[bf16x3 emulation, B-streamed] %d randomised tap / stride / epilogue cases agree with the native kernel '
                     'within 3e-5 rms per element' % done)
+
+
+def test_bstream_and_bxs_hand_one_relay_workspace_to_each_other(ops, monkeypatch):
+    """Both B-streamed kernels run ONE stream-K relay (csrc/stream_k_relay.h) on one workspace layout, so a workspace
+    zero-filled once may pass from one to the other: launch epochs, not resets, tell the launches apart.  The smallest 1x1
+    shape both kernels take with heads and tails on 256 CUs: M = 1 x 260 x 128 = 33 280 rows, K = 1024, 128 output channels ->
+    both pick the 128 x 128 tile: 260 tiles >= the grid, 260 x 8 iterations no multiple of it.  The native kernel is forced
+    (HND_DEBUG_PICKER=bstream_all) on the descriptor without the stream image, the emulated one runs on the descriptor with
+    it.  Nothing is provoked: no debug hook, the default spin limit."""
+    from hnd_ghnd_object_detectors_amd import _lib
+    L = _lib.load()
+    g = torch.Generator().manual_seed(11)
+    n, h, w, cin, cout = 1, 260, 128, 1024, 128
+    x = torch.randn(n, h, w, cin, generator=g).to(DEV)
+    pk = ops.pack_weights((torch.randn(cout, cin, 1, 1, generator=g) / 32.0).to(DEV))
+    monkeypatch.setenv('HND_BRES', '0')
+    monkeypatch.setenv('HND_DEBUG_PICKER', 'bstream_all')
+    ys = [torch.full((n, h, w, cout), float('nan'), device=DEV) for _ in range(2)]
+    with ops.emulation('off'):
+        ln = ops.conv_forward(x, pk, ys[0], 1, 1, 0, relu=True)
+    with ops.emulation('bxs'):
+        le = ops.conv_forward(x, pk, ys[1], 1, 1, 0, relu=True)
+    assert ln.variant == 'bstream_128' and le.variant.startswith('bxs'), (ln.variant, le.variant)
+    assert ln.relay is not None and le.relay is not None and ln.relay.numel() == le.relay.numel()
+    # (the grid from the workspace size: a deliberate restatement of relay_workspace_bytes -- no binding exposes the CU count)
+    grid = (ln.relay.numel() * 4 - 64) // (16384 * 4 + 4)
+    tiles, iters = (n * h * w // 128) * (cout // 128), cin // 128
+    assert tiles >= grid and (tiles * iters) % grid != 0, (tiles, iters, grid)     # the relay has heads and tails
+    L.hnd_relay_timeouts(1)
+    # each kernel on a workspace of its own, zero-filled once
+    fresh = []
+    for l, y in ((ln, ys[0]), (le, ys[1])):
+        l.run()
+        ops.sync_check()
+        assert not bool(torch.isnan(y).any())
+        fresh.append(y.clone())
+    # ... and back to back on a single one
+    ws = torch.zeros_like(ln.relay)
+    ln.desc.relay_ws = le.desc.relay_ws = ws.data_ptr()
+    for i in range(4):
+        ys[i % 2].fill_(float('nan'))
+        (ln, le)[i % 2].run()
+        ops.sync_check()
+        assert torch.equal(ys[i % 2], fresh[i % 2]), (i, (ln, le)[i % 2].variant)
+    assert L.hnd_relay_timeouts(0) == 0

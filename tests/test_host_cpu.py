@@ -287,9 +287,9 @@ def test_coco_format_loaders_without_pycocotools(tmp_path):
 
 
 def _relay_segments(T, kg8, G, lb):
-    """Python mirror of the work split of csrc/conv_bstream.hip (bstream_kernel, relay mode): the units
-    [U lb / G, U (lb + 1) / G) of the linear (tile, iteration) space as (tile, it0, it1, kind) segments in the order the
-    workgroup processes them: head first, whole tiles, tail last."""
+    """Python mirror of the work split of csrc/stream_k_relay.h (relay_split with a workspace + the kernels' seg_of; both
+    B-streamed kernels): the units [U lb / G, U (lb + 1) / G) of the linear (tile, iteration) space as (tile, it0, it1,
+    kind) segments in the order the workgroup processes them: head first, whole tiles, tail last."""
     U = T * kg8
     u0, u1 = U * lb // G, U * (lb + 1) // G
     tA, tB = u0 // kg8, u1 // kg8
