@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <type_traits>
 #include <utility>
 
@@ -67,6 +68,54 @@ __device__ __forceinline__ int xcd_contiguous_block() {
 }
 
 inline hipStream_t as_stream(void* s) { return (hipStream_t)s; }
+
+// Launch of a kernel that needs more than 64 KB of dynamic LDS: raises the kernel's limit to `attr_bytes` once per device
+// (the attribute lives on the device's function; one mask of devices per instantiation, i.e. per kernel), launches, and
+// returns check_launch(what).  `what` names the launch in both error texts.
+template <auto KERN, class... Args>
+int launch_big_lds(dim3 grid, dim3 block, size_t lds, int attr_bytes, hipStream_t stream, const char* what, const Args&... args) {
+  static std::atomic<unsigned long long> attr_set{0};
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  const unsigned long long bit = 1ull << (dev & 63);
+  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
+    hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, attr_bytes);
+    if (e != hipSuccess) {
+      set_error("hipFuncSetAttribute(%s) failed: %s", what, hipGetErrorString(e));
+      return HND_ERR_LAUNCH;
+    }
+    attr_set.fetch_or(bit, std::memory_order_relaxed);
+  }
+  hipLaunchKernelGGL(KERN, grid, block, lds, stream, args...);
+  return check_launch(what);
+}
+
+// The on/off (or numeric) environment switches: atoi of the value, `dflt` when unset.  Read per call: in-process A/B.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+// ... the two switches that are off when their value BEGINS with '0' (HND_BSTREAM, HND_BXS)
+inline bool env_begins_with_0(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '0';
+}
+
+// ---- host-side facts about a launch that several pickers and launches share
+// more than the one centred sample per output pixel (the kernels' TAPS builds)
+inline bool has_taps(const hnd_conv_desc& d) { return d.kh * d.kw > 1 || d.bh != 0 || d.bw != 0; }
+// every output pixel samples inside the input (what the tap-free builds assume)
+inline bool samples_inside(const hnd_conv_desc& d) {
+  return (long long)(d.oh - 1) * d.sh < d.h && (long long)(d.ow - 1) * d.sw < d.w_;
+}
+inline long long gemm_rows(const hnd_conv_desc& d) { return (long long)d.n * d.oh * d.ow; }
+// The B-resident kernels give every `bn`-column weight slice to one workgroup and the cout / bn workgroups of a TEAM to one
+// XCD: the number of teams, or 0 where the slices do not divide an XCD's CUs evenly
+inline int team_count(int cout, int bn) {
+  const int per_xcd = cu_count() / 8, nsl = cout / bn;
+  if (per_xcd < 1 || nsl < 1 || nsl > per_xcd || per_xcd % nsl != 0) return 0;
+  return 8 * (per_xcd / nsl);
+}
 
 // HND_DEBUG_PICKER: the ONE switch behind which the kernel pickers' experiment / test overrides live (A/B tools and the
 // bit-identity tests force a variant with it; nothing in normal use sets it).  Comma-separated keys, optionally key=value:

@@ -23,7 +23,6 @@
 //
 // Roofline: fp32 MFMA (157.3 TFLOP/s).  Per wave and k group: 64 MFMAs (2048 cycles of its SIMD's pipe at two
 // waves per SIMD: 4096) against 4 global_load_dwordx4 + 4 ds_read_b128 -- 8 B/clk/CU from L2, 4 % of the LDS.
-#include <atomic>
 
 #include "common.h"
 #include "conv_epilogue.h"
@@ -490,28 +489,10 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
   }
 }
 
-int bres_kmax() {
-  const char* e = getenv("HND_BRES");          // 0 = off, else the largest K taken (read per call: in-process A/B)
-  return e ? atoi(e) : 512;
-}
-
 template <int WN, int KQ, bool PRO>
 int launch_bres_t(const hnd_conv_desc& d, const BresArgs& a, size_t lds, int grid, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};
-  auto kern = bres_kernel<WN, KQ, PRO>;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(bres<%d,%d>) failed: %s", WN, KQ, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, stream, d, a);
-  return hnd::check_launch("hnd_conv2d_igemm(bres)");
+  return hnd::launch_big_lds<bres_kernel<WN, KQ, PRO>>(dim3(grid), dim3(512), lds, 160 * 1024, stream, "hnd_conv2d_igemm(bres)",
+                                                       d, a);
 }
 
 template <int WN, int KQ>
@@ -522,21 +503,8 @@ int launch_bres_p(const hnd_conv_desc& d, const BresArgs& a, size_t lds, int gri
 
 template <int WN, int KQ, bool PRO, bool RES>
 int launch_bres2_t(const hnd_conv_desc& d, const BresArgs& a, size_t lds, int grid, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};
-  auto kern = bres2_kernel<WN, KQ, PRO, RES>;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(bres2<%d,%d>) failed: %s", WN, KQ, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, d, a);
-  return hnd::check_launch("hnd_conv2d_igemm(bres2)");
+  return hnd::launch_big_lds<bres2_kernel<WN, KQ, PRO, RES>>(dim3(grid), dim3(256), lds, 160 * 1024, stream,
+                                                             "hnd_conv2d_igemm(bres2)", d, a);
 }
 
 template <int WN, int KQ>
@@ -553,7 +521,7 @@ namespace hnd {
 // 0 = not taken; 1 / 2 = the 8-wave kernel with a 64- / 128-column weight slice (K <= 512 / 256); 3 / 4 = the
 // one-wave-per-SIMD kernel (bres2) with a 64- / 128-column slice, for epilogues without a mask operand
 int bres_variant(const hnd_conv_desc& d) {
-  const int kmax = bres_kmax();
+  const int kmax = env_int("HND_BRES", 512);             // 0 = off, else the largest K taken
   if (kmax <= 0 || d.kh != 1 || d.kw != 1 || d.bh != 0 || d.bw != 0 || d.stats != nullptr) return 0;
   if (d.cin != d.kdim) return 0;
   if (d.w_group_rows % 64 != 0) return 0;
@@ -563,16 +531,13 @@ int bres_variant(const hnd_conv_desc& d) {
   if (wn == 2 ? (d.kdim != 64 && d.kdim != 128 && d.kdim != 256) : (d.kdim != 256 && d.kdim != 512)) return 0;
   const int bn = 64 * wn;
   if (d.cout % bn != 0) return 0;
-  const int per_xcd = hnd::cu_count() / 8, nsl = d.cout / bn;
-  if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return 0;
-  if ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_) return 0;
-  const long long M = (long long)d.n * d.oh * d.ow;
-  const long long nchunks = (M + 63) / 64, nteams = 8ll * (per_xcd / nsl);
-  const long long per_team = nchunks / nteams;
+  const long long nteams = team_count(d.cout, bn);
+  if (nteams == 0 || !samples_inside(d)) return 0;
+  const long long per_team = (gemm_rows(d) + 63) / 64 / nteams;
   const bool plain = !d.res2 && !d.mask && !d.mask_bits && !(d.res1 && d.pro_scale);  // one-wave kernel: optional res1 only
-  const char* v2 = getenv("HND_BRES2");                   // 0 = never the one-wave kernel (A/B)
+  const bool v2_on = env_int("HND_BRES2", 1) != 0;        // 0 = never the one-wave kernel (A/B)
   const bool all = hnd::debug_picker("bres_all") > 0;     // every eligible launch, not only where it was measured to win
-  if (plain && d.kdim >= 128 && !(v2 && atoi(v2) == 0) && per_team >= 2ll * (4 / wn)) {
+  if (plain && d.kdim >= 128 && v2_on && per_team >= 2ll * (4 / wn)) {
     // measured (profiles/r03_bres_vs_tiled.txt): the one-wave kernel wins on long runs of chunks; its prologue form
     // (8 VALU per A fragment beside a single wave's MFMAs) does not, and K = 512 needs >= 48 chunks per team
     const bool spills = (d.pro_scale || d.res1) && d.kdim == 512;      // those two builds do not fit 512 registers
@@ -596,20 +561,15 @@ int bres_variant(const hnd_conv_desc& d) {
   return wn;
 }
 
-int launch_bres(const hnd_conv_desc& d, hipStream_t stream) {
-  const int var = bres_variant(d);
-  if (var == 0) {
-    set_error("launch_bres: descriptor not eligible");
-    return HND_ERR_INVALID;
-  }
+// var: what bres_variant(d) returned (1 .. 4)
+int launch_bres(const hnd_conv_desc& d, int var, hipStream_t stream) {
   const bool v2 = var > 2;
   const int wn = v2 ? var - 2 : var;
-  const long long M = (long long)d.n * d.oh * d.ow;
   BresArgs a;
   a.div_ow = make_fastdiv((unsigned)d.ow);
   a.div_oh = make_fastdiv((unsigned)d.oh);
   a.nsl = d.cout / (64 * wn);
-  a.nchunks = (int)((M + 63) / 64);
+  a.nchunks = (int)((gemm_rows(d) + 63) / 64);
   a.cpg = d.w_group_rows / 64;
   const bool pro = d.pro_scale != nullptr;
   const size_t lds = ((size_t)64 * wn * d.kdim + (pro ? 2 * (size_t)d.kdim : 0) + 8 * 256) * sizeof(float);

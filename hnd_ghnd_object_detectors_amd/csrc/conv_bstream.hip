@@ -415,29 +415,21 @@ int* relay_error_word() {
 
 template <int WN, bool PRO, bool TAPS>
 int launch_t(const hnd_conv_desc& d, const BstreamArgs& a, size_t lds, int grid, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};
-  auto kern = bstream_kernel<WN, PRO, TAPS>;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(bstream<%d>) failed: %s", WN, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, d, a);
-  return hnd::check_launch("hnd_conv2d_igemm(bstream)");
+  return hnd::launch_big_lds<bstream_kernel<WN, PRO, TAPS>>(dim3(grid), dim3(256), lds, 160 * 1024, stream,
+                                                            "hnd_conv2d_igemm(bstream)", d, a);
 }
 
 template <int WN>
 int launch_w(const hnd_conv_desc& d, const BstreamArgs& a, size_t lds, int grid, hipStream_t stream) {
-  const bool taps = d.kh * d.kw > 1 || d.bh != 0 || d.bw != 0;
+  const bool taps = hnd::has_taps(d);
   if (d.pro_scale) return taps ? launch_t<WN, true, true>(d, a, lds, grid, stream)
                                : launch_t<WN, true, false>(d, a, lds, grid, stream);
   return taps ? launch_t<WN, false, true>(d, a, lds, grid, stream) : launch_t<WN, false, false>(d, a, lds, grid, stream);
+}
+
+// dynamic LDS of the build with `wn` wave columns: the picker's limit and the launch's size
+size_t bstream_lds_bytes(const hnd_conv_desc& d, int wn) {
+  return ((size_t)3 * 64 * wn * 64 + 2 * (size_t)d.cout + (d.pro_scale ? 2 * (size_t)d.cin : 0) + 4 * 128) * sizeof(float);
 }
 
 }  // namespace
@@ -446,22 +438,19 @@ namespace hnd {
 
 // 0 = not taken, 1 = 256 x 64 block tile (one wave column), 2 = 128 x 128 (two)
 int bstream_variant(const hnd_conv_desc& d) {
-  const char* e = getenv("HND_BSTREAM");                // 0 = off (A/B)
-  if (e && e[0] == '0') return 0;
+  if (env_begins_with_0("HND_BSTREAM")) return 0;       // 0 = off (A/B)
   const bool all = hnd::debug_picker("bstream_all") > 0;   // every eligible launch (A/B tools, tests)
   if (d.stats != nullptr || d.cin % 32 != 0) return 0;
   if (d.kdim % 128 != 0 || d.kdim < 256) return 0;
-  const bool taps = d.kh * d.kw > 1 || d.bh != 0 || d.bw != 0;
+  const bool taps = has_taps(d);
   if (taps ? (d.cin % 128 != 0 || d.kdim != d.kh * d.kw * d.cin) : (d.kdim != d.cin)) return 0;
-  if (!taps && ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_)) return 0;
+  if (!taps && !samples_inside(d)) return 0;
   if (d.cout % 64 != 0 || d.cout > 4096 || d.cin > 4096) return 0;
   if ((long long)d.n * d.h * d.w_ * d.cin >= (1ll << 32)) return 0;      // 32-bit pixel arithmetic on the tap path
   const int wn = d.cout % 128 == 0 ? 2 : 1;
   const int bm = 64 * (4 / wn);
   if (d.w_group_rows % bm != 0) return 0;
-  const size_t lds = ((size_t)3 * 64 * wn * 64 + 2 * (size_t)d.cout + (d.pro_scale ? 2 * (size_t)d.cin : 0) + 4 * 128) *
-                     sizeof(float);
-  if (lds > 160 * 1024) return 0;
+  if (bstream_lds_bytes(d, wn) > 160 * 1024) return 0;
   if (all) return wn;
   // Where it is taken by default (round 3, batch 16, per-launch HIP events of the step, tiled -> this kernel): the
   // stride-2 3x3 convs over taps (1.39 -> 1.24 ms, 1.45 -> 1.24 ms), the K = 2048 1x1 convs and data gradients of layer4
@@ -485,8 +474,6 @@ int bstream_variant(const hnd_conv_desc& d) {
   return wn;
 }
 
-size_t bstream_workspace(const hnd_conv_desc& d) { return relay_workspace(d, bstream_variant(d)); }
-
 // (stream_k_relay.h) one sticky error word for both B-streamed kernels
 int relay_launch_check(const char* kernel, int& spin_limit, int*& err) {
   if (__atomic_load_n(relay_error_word(), __ATOMIC_RELAXED) != 0) {
@@ -496,7 +483,7 @@ int relay_launch_check(const char* kernel, int& spin_limit, int*& err) {
   }
   err = g_err_dev;
   spin_limit = 1 << 21;
-  if (const char* e = getenv("HND_BSTREAM_SPIN")) spin_limit = atoi(e) > 0 ? atoi(e) : spin_limit;
+  if (const int spin = env_int("HND_BSTREAM_SPIN", 0); spin > 0) spin_limit = spin;
   return HND_OK;
 }
 
@@ -508,13 +495,8 @@ int relay_timeouts(int reset) {
   return v;
 }
 
-int launch_bstream(const hnd_conv_desc& d, hipStream_t stream) {
-  const int wn = bstream_variant(d);
-  if (wn == 0) {
-    set_error("launch_bstream: descriptor not eligible");
-    return HND_ERR_INVALID;
-  }
-  const int bn = 64 * wn;
+// wn: what bstream_variant(d) returned (1 / 2)
+int launch_bstream(const hnd_conv_desc& d, int wn, hipStream_t stream) {
   BstreamArgs a;
   int grid;
   if (const int rc = relay_launch_check("bstream", a.spin_limit, a.err)) return rc;
@@ -522,10 +504,9 @@ int launch_bstream(const hnd_conv_desc& d, hipStream_t stream) {
   a.div_oh = make_fastdiv((unsigned)d.oh);
   relay_grid(d, wn, a.mtiles, a.ntiles, grid);
   a.kg8 = d.kdim / 128;
-  a.dbg = getenv("HND_BSTREAM_DBG") ? atoi(getenv("HND_BSTREAM_DBG")) : 0;
-  a.relay = (d.relay_ws && bstream_workspace(d) > 0) ? d.relay_ws : nullptr;
-  const size_t lds = ((size_t)3 * bn * 64 + 2 * (size_t)d.cout + (d.pro_scale ? 2 * (size_t)d.cin : 0) + 4 * 128) *
-                     sizeof(float);
+  a.dbg = env_int("HND_BSTREAM_DBG", 0);
+  a.relay = (d.relay_ws && relay_workspace(d, wn) > 0) ? d.relay_ws : nullptr;
+  const size_t lds = bstream_lds_bytes(d, wn);
   return wn == 2 ? launch_w<2>(d, a, lds, grid, stream) : launch_w<1>(d, a, lds, grid, stream);
 }
 

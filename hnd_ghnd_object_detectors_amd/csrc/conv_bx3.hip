@@ -21,7 +21,6 @@
 //
 // Roofline: bf16 MFMA at 6 products = 2.5 PFLOP/s / 6 = 0.42 PFLOP/s-equivalent of fp32 work, 2.7x the fp32 MFMA peak;
 // at K = N = 256 the operands' 4 M (K + N) bytes bound a launch at 0.35 ms of HBM time against 0.34 ms of matrix time.
-#include <atomic>
 
 #include "bf16x3.h"
 #include "common.h"
@@ -374,22 +373,9 @@ __global__ void pack_bx3_kernel(const float* __restrict__ w, uint16_t* __restric
 
 template <int KS, bool RES, bool MO, bool MK = false>
 int launch_bx3_t(const hnd_conv_desc& d, const Bx3Args& a, int grid, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};
-  auto kern = bx3_kernel<KS, RES, MO, MK>;
   const size_t lds = (size_t)3 * 64 * 32 * KS * sizeof(uint16_t);
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(bx3<%d>) failed: %s", KS, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, d, a);
-  return hnd::check_launch("hnd_conv2d_igemm(bx3)");
+  return hnd::launch_big_lds<bx3_kernel<KS, RES, MO, MK>>(dim3(grid), dim3(256), lds, 160 * 1024, stream, "hnd_conv2d_igemm(bx3)",
+                                                          d, a);
 }
 
 }  // namespace
@@ -406,9 +392,8 @@ static bool bx3_recommended(long long rows_per_image, int kdim, int cout) {
   if (kdim != 128 && (kdim % 256 != 0 || kdim > 2048)) return false;
   // (round 6 A/B, same box, img/s at batch 16 / batch 4: K >= 1024 launches on the B-streamed build instead 214.2 / 170.7,
   // K >= 512 210.5 / 161.2, as shipped 216.2 / 176.6 -- the passes over k stay)
-  const int per_xcd = cu_count() / 8, nsl = cout / 64;
-  if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return false;
-  const long long nteams = 8ll * (per_xcd / nsl);
+  const long long nteams = team_count(cout, 64);
+  if (nteams == 0) return false;
   const long long chunks_at_16 = (rows_per_image * 16 + 63) / 64;
   return chunks_at_16 / nteams >= (kdim > 512 ? 16 : 8);
 }
@@ -430,11 +415,10 @@ bool bx3_applies(const hnd_conv_desc& d) {
   // a residual of y's geometry, or the exactly 2x coarser map of the FPN's top-down path (whole 4-pixel groups per row)
   if (d.res1 && d.res1_mode == 1 && (d.yh != 2 * d.res1_h || d.yw != 2 * d.res1_w || d.ow % 4 != 0)) return false;
   if (d.cout % 64 != 0 || d.ldc % 4 != 0 || ((uintptr_t)d.y % 16) != 0) return false;
-  const int per_xcd = cu_count() / 8, nsl = d.cout / 64;
-  if (per_xcd < 1 || nsl > per_xcd || per_xcd % nsl != 0) return false;
+  if (team_count(d.cout, 64) == 0) return false;
   if (d.y_sh != 1 || d.y_sw != 1 || d.y_oh != 0 || d.y_ow != 0 || d.yh != d.oh || d.yw != d.ow) return false;
-  if ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_) return false;
-  const long long M = (long long)d.n * d.oh * d.ow;
+  if (!samples_inside(d)) return false;
+  const long long M = gemm_rows(d);
   if (M < 64 || d.w_group_rows % 64 != 0) return false;
   if (M % 64 != 0 && d.w_group_rows != 0) return false;      // (a tail: one weight group)
   return true;
@@ -445,7 +429,7 @@ static int launch_bx3_one(const hnd_conv_desc& d, int kpart, hipStream_t stream)
   a.div_ow = make_fastdiv((unsigned)d.ow);
   a.div_oh = make_fastdiv((unsigned)d.oh);
   a.nsl = d.cout / 64;
-  a.mrows = (int)((long long)d.n * d.oh * d.ow);
+  a.mrows = (int)gemm_rows(d);
   a.nchunks = (a.mrows + 63) / 64;
   a.cpg = d.w_group_rows / 64;
   a.res_up = d.res1 && d.res1_mode == 1;
@@ -485,11 +469,9 @@ int launch_bx3_tiled(const hnd_conv_desc& d, int mi, hipStream_t stream);      /
 static const int BX3_TILED_BELOW_K128 = 3, BX3_TILED_BELOW_K256 = 3, BX3_TILED_BELOW_K512 = 10, BX3_TILED_BELOW_KLONG = 16;
 static const int BX3_TILED_128_ROWS_FROM = 10;
 
-// 0 = persistent, 1 / 2 = tiled with a 64- / 128-row tile
-static int bx3_pick(const hnd_conv_desc& d) {
-  if (!bx3_applies(d)) return 0;
-  const long long M = (long long)d.n * d.oh * d.ow, chunks = (M + 63) / 64;
-  const long long nteams = 8ll * ((cu_count() / 8) / (d.cout / 64));
+// 0 = persistent, 1 / 2 = tiled with a 64- / 128-row tile.  For a launch bx3_applies admits (pick_conv asks in that order).
+int bx3_build(const hnd_conv_desc& d) {
+  const long long chunks = (gemm_rows(d) + 63) / 64, nteams = team_count(d.cout, 64);
   const long long per_team = (chunks + nteams - 1) / nteams;
   const bool is_long = d.kdim >= 1024;
   const int rows = is_long && per_team >= BX3_TILED_128_ROWS_FROM ? 2 : 1;
@@ -504,21 +486,16 @@ static int bx3_pick(const hnd_conv_desc& d) {
   return per_team < below ? rows : 0;
 }
 
-int bx3_build(const hnd_conv_desc& d) { return bx3_pick(d) ? 1 : 0; }
-
-int launch_bx3(const hnd_conv_desc& d, hipStream_t stream) {
-  if (!bx3_applies(d)) {
-    set_error("launch_bx3: descriptor not eligible");
-    return HND_ERR_INVALID;
-  }
-  if (const int rows = bx3_pick(d)) return launch_bx3_tiled(d, rows, stream);
+// build: what bx3_build(d) returned
+int launch_bx3(const hnd_conv_desc& d, int build, hipStream_t stream) {
+  if (build) return launch_bx3_tiled(d, build, stream);
   if (d.kdim <= 256) return launch_bx3_one(d, d.kdim, stream);
   // K = 256 P: the resident slice of three planes holds 256 k.  Pass 1: k 0 .. 255, y = acc * scale + shift (+ the launch's
   // own residual; no ReLU, no mask); pass p: k 256 (p - 1) .. with res1 = y: y = acc * scale + y; the last pass applies the
   // ReLU-backward mask, the ReLU and writes the mask nibbles.  The kernel takes the row stride of x from cin and the depth
   // from its template, so a later pass is the same launch 256 floats further on.  (fp32 partial sums in y between passes:
   // what the accumulator holds anyway)
-  const long long groups = d.w_group_rows > 0 ? ((long long)d.n * d.oh * d.ow) / d.w_group_rows : 1;
+  const long long groups = d.w_group_rows > 0 ? gemm_rows(d) / d.w_group_rows : 1;
   const int parts = d.kdim / 256;
   const size_t part_elems = (size_t)groups * (size_t)(d.cout / 64) * (size_t)3 * 64 * 256;
   for (int p = 0; p < parts; ++p) {

@@ -261,7 +261,7 @@ int launch_bx3t_t(const hnd_conv_desc& d, hipStream_t stream) {
 
 namespace hnd {
 
-// The caller (launch_bx3) has checked bx3_applies: this build takes everything it admits.
+// mi: bx3_build's 1 / 2 (a 64- / 128-row tile); this build takes everything bx3_applies admits.
 int launch_bx3_tiled(const hnd_conv_desc& d, int mi, hipStream_t stream) {
   return mi == 1 ? launch_bx3t_t<1>(d, stream) : launch_bx3t_t<2>(d, stream);
 }

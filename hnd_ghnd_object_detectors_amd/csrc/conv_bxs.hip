@@ -21,7 +21,6 @@
 // pieces of stage 2 i + 2 + u / 2] then the 8 ring loads of step s + 4.  The wait for ring slot s + 1 (issued at step s - 3)
 // therefore allows 24 + (u even ? 2 : 1) NBL younger operations, the wait for stage 2 i + u / 2 (issued at step s - 4)
 // 32 + NBL.  Epilogue loads / stores between two tiles are younger still: they only make these waits stricter.
-#include <atomic>
 
 #include "bf16x3.h"
 #include "common.h"
@@ -499,26 +498,13 @@ __global__ void pack_bxs_kernel(const float* __restrict__ w, uint16_t* __restric
 
 template <int WN, bool PRO, bool TAPS>
 int launch_t(const hnd_conv_desc& d, const BxsArgs& a, size_t lds, int grid, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};
-  auto kern = bxs_kernel<WN, PRO, TAPS>;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(bxs<%d>) failed: %s", WN, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, d, a);
-  return hnd::check_launch("hnd_conv2d_igemm(bxs)");
+  return hnd::launch_big_lds<bxs_kernel<WN, PRO, TAPS>>(dim3(grid), dim3(256), lds, 160 * 1024, stream, "hnd_conv2d_igemm(bxs)",
+                                                        d, a);
 }
 
 template <int WN>
 int launch_w(const hnd_conv_desc& d, const BxsArgs& a, size_t lds, int grid, hipStream_t stream) {
-  const bool taps = d.kh * d.kw > 1 || d.bh != 0 || d.bw != 0;
+  const bool taps = hnd::has_taps(d);
   if (d.pro_scale) return taps ? launch_t<WN, true, true>(d, a, lds, grid, stream)
                                : launch_t<WN, true, false>(d, a, lds, grid, stream);
   return taps ? launch_t<WN, false, true>(d, a, lds, grid, stream) : launch_t<WN, false, false>(d, a, lds, grid, stream);
@@ -538,9 +524,9 @@ namespace hnd {
 int bxs_variant(const hnd_conv_desc& d) {
   if (!d.w_bf16x3s) return 0;
   if (d.cin % 64 != 0 || d.kdim % 128 != 0 || d.kdim < 128) return 0;
-  const bool taps = d.kh * d.kw > 1 || d.bh != 0 || d.bw != 0;
+  const bool taps = has_taps(d);
   if (taps ? (d.kdim != d.kh * d.kw * d.cin) : (d.kdim != d.cin)) return 0;
-  if (!taps && ((long long)(d.oh - 1) * d.sh >= d.h || (long long)(d.ow - 1) * d.sw >= d.w_)) return 0;
+  if (!taps && !samples_inside(d)) return 0;
   if (d.cout % 64 != 0 || d.cout > 4096 || d.cin > 4096) return 0;
   if ((long long)d.n * d.h * d.w_ * d.cin >= (1ll << 32)) return 0;      // 32-bit pixel arithmetic on the tap path
   // 128 x 128 tiles where the output has whole 128-column blocks, else 256 x 64 (HND_DEBUG_PICKER=bxs_wn1: always the
@@ -553,14 +539,8 @@ int bxs_variant(const hnd_conv_desc& d) {
   return wn;
 }
 
-size_t bxs_workspace(const hnd_conv_desc& d) { return relay_workspace(d, bxs_variant(d)); }
-
-int launch_bxs(const hnd_conv_desc& d, hipStream_t stream) {
-  const int wn = bxs_variant(d);
-  if (wn == 0) {
-    set_error("launch_bxs: descriptor not eligible");
-    return HND_ERR_INVALID;
-  }
+// wn: what bxs_variant(d) returned (1 / 2)
+int launch_bxs(const hnd_conv_desc& d, int wn, hipStream_t stream) {
   BxsArgs a;
   int grid;
   if (const int rc = relay_launch_check("bxs", a.spin_limit, a.err)) return rc;
@@ -570,7 +550,7 @@ int launch_bxs(const hnd_conv_desc& d, hipStream_t stream) {
   a.div_kw = make_fastdiv((unsigned)d.kw);
   relay_grid(d, wn, a.mtiles, a.ntiles, grid);
   a.nit = d.kdim / 128;
-  a.relay = (d.relay_ws && bxs_workspace(d) > 0) ? d.relay_ws : nullptr;
+  a.relay = (d.relay_ws && relay_workspace(d, wn) > 0) ? d.relay_ws : nullptr;
   const size_t lds = bxs_lds_bytes(d, wn);
   return wn == 2 ? launch_w<2>(d, a, lds, grid, stream) : launch_w<1>(d, a, lds, grid, stream);
 }
@@ -584,7 +564,7 @@ int launch_bxs(const hnd_conv_desc& d, hipStream_t stream) {
 extern "C" int hnd_bf16x3s_recommended(int64_t rows_per_image, int kdim, int cout, int taps) {
   (void)taps;
   if (rows_per_image <= 0 || cout <= 0 || cout % 64 != 0 || kdim % 128 != 0) return 0;
-  if (const char* e = getenv("HND_BXS")) if (e[0] == '0') return 0;       // A/B: the native B-streamed / tiled kernels
+  if (hnd::env_begins_with_0("HND_BXS")) return 0;                        // A/B: the native B-streamed / tiled kernels
   return (rows_per_image * 16 >= 16384 && kdim >= 256) ? 1 : 0;
 }
 

@@ -25,10 +25,10 @@
 //
 // Roofline: compute bound on the fp32 matrix pipe (157.3 TFLOP/s): per block k-step 128*BN*32*2
 // flop vs (128+BN)*32*4 B staged => 64 flop/B at BN=128.
-#include <atomic>
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "stream_k_relay.h"
 
 #include <stdlib.h>
 
@@ -486,15 +486,13 @@ __global__ void __launch_bounds__(128, 4) thin_n_kernel(const hnd_conv_desc d) {
 }
 
 bool thin_n_applies(const hnd_conv_desc& d) {
-  static const int on = getenv("HND_THIN_N") ? atoi(getenv("HND_THIN_N")) : 1;
-  return on && !d.mask_bits && !d.mask_out && !d.bwd_x && d.cin != 4 && d.cin % 64 == 0 && d.cout <= 4 && d.res1_mode == 0 &&
+  return hnd::env_int("HND_THIN_N", 1) && !d.mask_bits && !d.mask_out && !d.bwd_x && d.cin != 4 && d.cin % 64 == 0 && d.cout <= 4 && d.res1_mode == 0 &&
          d.w_group_rows == 0 &&
          d.kdim == d.kh * d.kw * d.cin && d.kdim <= 4096;
 }
 
 int launch_thin_n(const hnd_conv_desc& d, hipStream_t stream) {
-  const long long M = (long long)d.n * d.oh * d.ow;
-  const int mtiles = (int)((M + 127) / 128);
+  const int mtiles = (int)((hnd::gemm_rows(d) + 127) / 128);
   const size_t lds = ((size_t)128 * THIN_LDA + 3 * 128) * sizeof(float);
   if (d.pro_scale) hipLaunchKernelGGL(thin_n_kernel<true>, dim3(mtiles), dim3(128), lds, stream, d);
   else hipLaunchKernelGGL(thin_n_kernel<false>, dim3(mtiles), dim3(128), lds, stream, d);
@@ -503,25 +501,11 @@ int launch_thin_n(const hnd_conv_desc& d, hipStream_t stream) {
 
 template <int BM, int BN, int BK, bool CIN4, bool PRO>
 int launch_pro(const hnd_conv_desc& d, hipStream_t stream) {
-  static std::atomic<unsigned long long> attr_set{0};    // per device: the attribute lives on the device's function
-  auto kern = igemm_kernel<BM, BN, BK, CIN4, PRO>;
   const size_t lds = lds_bytes<BM, BN, BK, PRO>();
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const unsigned long long bit = 1ull << (dev & 63);
-  if (!(attr_set.load(std::memory_order_relaxed) & bit)) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      hnd::set_error("hipFuncSetAttribute(igemm<%d,%d>) failed: %s", BM, BN, hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_set.fetch_or(bit, std::memory_order_relaxed);
-  }
-  const long long M = (long long)d.n * d.oh * d.ow;
-  const int mtiles = (int)((M + BM - 1) / BM);
+  const int mtiles = (int)((hnd::gemm_rows(d) + BM - 1) / BM);
   const int ntiles = (d.cout + BN - 1) / BN;
-  hipLaunchKernelGGL(kern, dim3(mtiles * ntiles), dim3(256), lds, stream, d, ntiles);
-  return hnd::check_launch("hnd_conv2d_igemm");
+  return hnd::launch_big_lds<igemm_kernel<BM, BN, BK, CIN4, PRO>>(dim3(mtiles * ntiles), dim3(256), lds, (int)lds, stream,
+                                                                  "hnd_conv2d_igemm", d, ntiles);
 }
 
 // Tile choice.  Resident blocks: 2 per CU for every tile but 64x64 (4 per CU).  A launch runs in
@@ -545,7 +529,7 @@ int pick_tile(const hnd_conv_desc& d) {
       return t;
     }
   }
-  const long long M = (long long)d.n * d.oh * d.ow;
+  const long long M = hnd::gemm_rows(d);
   const bool n128 = d.cout % 128 == 0;
   // eff: large-grid throughput relative to the 128x128 tile (128.6 / 115.6 / 117.1 / 113.8 TFLOP/s measured on a
   // 16800-tile 3x3 conv with tools/bench_conv.py); bpc: resident blocks per CU of the build in use.
@@ -579,20 +563,61 @@ int pick_tile(const hnd_conv_desc& d) {
 }  // namespace
 
 namespace hnd {
+// Each kernel's rule lives with the kernel (0 / false = not taken, else the variant its launch is given); pick_conv below is
+// the one place they are asked, in order.
 int bres_variant(const hnd_conv_desc& d);                      // conv_bres.hip: B-resident persistent GEMM
-int launch_bres(const hnd_conv_desc& d, hipStream_t stream);
+int launch_bres(const hnd_conv_desc& d, int var, hipStream_t stream);
 bool stem7_applies(const hnd_conv_desc& d);                    // conv_stem.hip: 7x7 s2 stem from an LDS patch
 int launch_stem7(const hnd_conv_desc& d, hipStream_t stream);
 int bstream_variant(const hnd_conv_desc& d);                   // conv_bstream.hip: B-streamed persistent GEMM (long K)
-int launch_bstream(const hnd_conv_desc& d, hipStream_t stream);
-size_t bstream_workspace(const hnd_conv_desc& d);
+int launch_bstream(const hnd_conv_desc& d, int wn, hipStream_t stream);
 bool bx3_applies(const hnd_conv_desc& d);                      // conv_bx3.hip: fp32 emulated on the bf16 pipe, B resident
-int launch_bx3(const hnd_conv_desc& d, hipStream_t stream);
-int bx3_build(const hnd_conv_desc& d);                         // ... its persistent (0) or tiled (1) build: the same bits
+int bx3_build(const hnd_conv_desc& d);                         // ... its persistent (0) or tiled (1 / 2) build: the same bits
+int launch_bx3(const hnd_conv_desc& d, int build, hipStream_t stream);
 int bxs_variant(const hnd_conv_desc& d);                       // conv_bxs.hip: ... B streamed (taps, long K, any epilogue)
-int launch_bxs(const hnd_conv_desc& d, hipStream_t stream);
-size_t bxs_workspace(const hnd_conv_desc& d);
+int launch_bxs(const hnd_conv_desc& d, int wn, hipStream_t stream);
 }  // namespace hnd
+
+namespace {
+
+// The kernel that runs a launch and the variant it runs in -- decided HERE, once: hnd_conv2d_igemm launches what pick_conv
+// returns, and the tile / build / workspace queries are fields of the same pick, so they cannot disagree with it.
+enum ConvKernel { STEM7, CIN4_TILE, THIN_N, BX3, BXS, BRES, BSTREAM, TILED, CONV_KERNELS };
+struct ConvPick {
+  ConvKernel kernel;
+  int variant;          // what bx3_build / bxs_variant / bres_variant / bstream_variant / pick_tile returned; else 0
+};
+
+ConvPick pick_conv(const hnd_conv_desc& d) {
+  if (d.cin == 4) return {hnd::stem7_applies(d) ? STEM7 : CIN4_TILE, 0};   // the 3->64 decoder conv and any other 4-channel input
+  if (thin_n_applies(d)) return {THIN_N, 0};
+  if (hnd::bx3_applies(d)) return {BX3, hnd::bx3_build(d)};             // only with hnd_conv_desc.w_bf16x3 attached
+  if (const int v = hnd::bxs_variant(d)) return {BXS, v};               // only with hnd_conv_desc.w_bf16x3s attached
+  if (const int v = hnd::bres_variant(d)) return {BRES, v};
+  if (const int v = hnd::bstream_variant(d)) return {BSTREAM, v};
+  return {TILED, pick_tile(d)};
+}
+
+// hnd_conv2d_igemm_tile's code (include/hnd_hip.h) by kernel and variant; -1: no such variant.  10 is unused.
+int tile_code(ConvPick p) {
+  static const signed char code[CONV_KERNELS][5] = {
+      /* STEM7     */ {9, -1, -1, -1, -1},
+      /* CIN4_TILE */ {1, -1, -1, -1, -1},
+      /* THIN_N    */ {4, -1, -1, -1, -1},
+      /* BX3       */ {13, 13, 13, -1, -1},      // one code for both builds (hnd_conv2d_igemm_build tells them apart)
+      /* BXS       */ {-1, 15, 14, -1, -1},
+      /* BRES      */ {-1, 6, 5, 8, 7},
+      /* BSTREAM   */ {-1, 12, 11, -1, -1},
+      /* TILED     */ {0, 1, 2, 3, -1}};
+  return code[p.kernel][p.variant];
+}
+int build_code(ConvPick p) { return p.kernel == BX3 && p.variant ? 1 : 0; }
+// bytes of relay workspace: the two B-streamed kernels, when every workgroup gets at least one tile
+size_t relay_bytes(const hnd_conv_desc& d, ConvPick p) {
+  return p.kernel == BXS || p.kernel == BSTREAM ? hnd::relay_workspace(d, p.variant) : 0;
+}
+
+}  // namespace
 
 extern "C" int hnd_conv2d_igemm(const hnd_conv_desc* desc, void* stream) {
   HND_REQUIRE(desc != nullptr, "hnd_conv2d_igemm: null descriptor");
@@ -624,16 +649,18 @@ extern "C" int hnd_conv2d_igemm(const hnd_conv_desc* desc, void* stream) {
                            !d.mask && !d.mask_bits && !d.relu && d.cin != 4),
               "hnd_conv2d_igemm: bwd_x needs stats + the four per-channel vectors and a plain epilogue");
   hipStream_t s = hnd::as_stream(stream);
-  if (d.cin == 4) {
-    if (hnd::stem7_applies(d)) return hnd::launch_stem7(d, s);
-    return launch<128, 64, 32, true>(d, s);   // the 3->64 decoder conv (and any other 4-channel-input conv)
+  const ConvPick p = pick_conv(d);
+  switch (p.kernel) {
+    case STEM7: return hnd::launch_stem7(d, s);
+    case CIN4_TILE: return launch<128, 64, 32, true>(d, s);
+    case THIN_N: return launch_thin_n(d, s);
+    case BX3: return hnd::launch_bx3(d, p.variant, s);
+    case BXS: return hnd::launch_bxs(d, p.variant, s);
+    case BRES: return hnd::launch_bres(d, p.variant, s);
+    case BSTREAM: return hnd::launch_bstream(d, p.variant, s);
+    default: break;
   }
-  if (thin_n_applies(d)) return launch_thin_n(d, s);
-  if (hnd::bx3_applies(d)) return hnd::launch_bx3(d, s);        // only with hnd_conv_desc.w_bf16x3 attached
-  if (hnd::bxs_variant(d)) return hnd::launch_bxs(d, s);        // only with hnd_conv_desc.w_bf16x3s attached
-  if (hnd::bres_variant(d)) return hnd::launch_bres(d, s);
-  if (hnd::bstream_variant(d)) return hnd::launch_bstream(d, s);
-  switch (pick_tile(d)) {
+  switch (p.variant) {
     case 0: return launch<128, 128, 16, false>(d, s);
     case 1: return launch<128, 64, 16, false>(d, s);
     case 2: return launch<64, 128, 16, false>(d, s);
@@ -642,25 +669,9 @@ extern "C" int hnd_conv2d_igemm(const hnd_conv_desc* desc, void* stream) {
 }
 
 extern "C" size_t hnd_conv2d_igemm_workspace(const hnd_conv_desc* desc) {
-  if (!desc || desc->cin == 4 || thin_n_applies(*desc) || hnd::bx3_applies(*desc)) return 0;
-  if (hnd::bxs_variant(*desc)) return hnd::bxs_workspace(*desc);
-  if (hnd::bres_variant(*desc)) return 0;
-  return hnd::bstream_workspace(*desc);
+  return desc ? relay_bytes(*desc, pick_conv(*desc)) : 0;
 }
 
-extern "C" int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc) {
-  if (!desc) return -1;
-  if (desc->cin == 4) return hnd::stem7_applies(*desc) ? 9 : 1;
-  if (thin_n_applies(*desc)) return 4;
-  if (hnd::bx3_applies(*desc)) return 13;
-  if (const int v = hnd::bxs_variant(*desc)) return v == 2 ? 14 : 15;
-  if (const int v = hnd::bres_variant(*desc)) return v == 2 ? 5 : (v == 1 ? 6 : (v == 4 ? 7 : 8));
-  if (const int v = hnd::bstream_variant(*desc)) return v == 2 ? 11 : 12;
-  return pick_tile(*desc);
-}
+extern "C" int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc) { return desc ? tile_code(pick_conv(*desc)) : -1; }
 
-extern "C" int hnd_conv2d_igemm_build(const hnd_conv_desc* desc) {
-  if (!desc) return -1;
-  if (desc->cin == 4 || thin_n_applies(*desc)) return 0;
-  return hnd::bx3_build(*desc);
-}
+extern "C" int hnd_conv2d_igemm_build(const hnd_conv_desc* desc) { return desc ? build_code(pick_conv(*desc)) : -1; }

@@ -335,10 +335,7 @@ __global__ void __launch_bounds__(256, 3) stem7_wgrad_kernel(const hnd_wgrad_des
 
 namespace hnd {
 
-static bool stem7_on() {                // HND_STEM7=0: the generic kernels (A/B, bit-identity tests)
-  const char* e = getenv("HND_STEM7");
-  return !(e && atoi(e) == 0);
-}
+static bool stem7_on() { return env_int("HND_STEM7", 1) != 0; }     // 0: the generic kernels (A/B, bit-identity tests)
 
 bool stem7_applies(const hnd_conv_desc& d) {
   if (!stem7_on()) return false;
@@ -349,27 +346,13 @@ bool stem7_applies(const hnd_conv_desc& d) {
 }
 
 int launch_stem7(const hnd_conv_desc& d, hipStream_t stream) {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   const size_t lds = ((size_t)PH * PW * 4 + 64 * WLD) * sizeof(float);
-  if (!attr_done[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem7_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(stem7) failed: %s", hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_done[dev & 63] = true;
-  }
   const int tiles_x = (d.ow + TW - 1) / TW, tiles_y = (d.oh + TH - 1) / TH;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int ntiles = d.n * tiles_x * tiles_y;
+  const int ntiles = d.n * tiles_x * tiles_y, cus = cu_count();
   const int grid = ntiles < 2 * cus ? ntiles : 2 * cus;        // persistent: two workgroups per CU walk the tiles
-  hipLaunchKernelGGL(stem7_kernel, dim3((unsigned)grid), dim3(256), lds, stream, d, tiles_x, tiles_y);
-  return check_launch("hnd_conv2d_igemm(stem7)");
+  return launch_big_lds<stem7_kernel>(dim3((unsigned)grid), dim3(256), lds, (int)lds, stream, "hnd_conv2d_igemm(stem7)", d,
+                                      tiles_x, tiles_y);
 }
-
 
 bool stem7_wgrad_applies(const hnd_wgrad_desc& d) {
   if (!stem7_on()) return false;
@@ -379,37 +362,19 @@ bool stem7_wgrad_applies(const hnd_wgrad_desc& d) {
 }
 
 int stem7_wgrad_blocks(const hnd_wgrad_desc& d) {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int ntiles = d.n * ((d.ow + WTW - 1) / WTW) * ((d.oh + WTH - 1) / WTH);
+  const int ntiles = d.n * ((d.ow + WTW - 1) / WTW) * ((d.oh + WTH - 1) / WTH), cus = cu_count();
   return ntiles < 3 * cus ? ntiles : 3 * cus;        // persistent: three workgroups per CU walk the tiles
 }
 
 // writes stem7_wgrad_blocks(d) slabs of [64][ncols_pad] floats into d.slabs
 int launch_stem7_wgrad(const hnd_wgrad_desc& d, int ncols_pad, hipStream_t stream) {
-  static bool attr_done[64] = {};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   const size_t lds = ((size_t)((WPH * WPW * 4 + 3) & ~3) + 64 * DYLD) * sizeof(float);
-  if (!attr_done[dev & 63]) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem7_wgrad_kernel<10>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      e = hipFuncSetAttribute((const void*)stem7_wgrad_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(stem7_wgrad) failed: %s", hipGetErrorString(e));
-      return HND_ERR_LAUNCH;
-    }
-    attr_done[dev & 63] = true;
-  }
   const int tiles_x = (d.ow + WTW - 1) / WTW, tiles_y = (d.oh + WTH - 1) / WTH;
+  const dim3 grid((unsigned)stem7_wgrad_blocks(d));
+  const char* what = "hnd_conv2d_wgrad(stem7)";
   if (d.cin_real == 3)
-    hipLaunchKernelGGL(stem7_wgrad_kernel<10>, dim3((unsigned)stem7_wgrad_blocks(d)), dim3(256), lds, stream, d, tiles_x,
-                       tiles_y, ncols_pad);
-  else
-    hipLaunchKernelGGL(stem7_wgrad_kernel<13>, dim3((unsigned)stem7_wgrad_blocks(d)), dim3(256), lds, stream, d, tiles_x,
-                       tiles_y, ncols_pad);
-  return check_launch("hnd_conv2d_wgrad(stem7)");
+    return launch_big_lds<stem7_wgrad_kernel<10>>(grid, dim3(256), lds, (int)lds, stream, what, d, tiles_x, tiles_y, ncols_pad);
+  return launch_big_lds<stem7_wgrad_kernel<13>>(grid, dim3(256), lds, (int)lds, stream, what, d, tiles_x, tiles_y, ncols_pad);
 }
 
 }  // namespace hnd

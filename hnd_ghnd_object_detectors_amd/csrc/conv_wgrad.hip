@@ -18,6 +18,8 @@
 #include <math.h>
 #include <stdlib.h>
 
+#include <algorithm>
+
 namespace {
 
 using hnd::FastDiv;
@@ -355,8 +357,8 @@ __global__ void __launch_bounds__(256) thin_wgrad_kernel(const ThinWgradArgs a) 
 }
 
 bool thin_wgrad_applies(const hnd_wgrad_desc& d, bool& thick_is_x) {
-  const char* e = getenv("HND_THIN_WGRAD");           // 0 = the MFMA kernel (read per call: in-process A/B)
-  if ((e && atoi(e) == 0) || d.kh != 2 || d.kw != 2 || d.stride != 1 || d.groups > 1 || (d.pad != 0 && d.pad != 1)) return false;
+  // HND_THIN_WGRAD=0: the MFMA kernel
+  if (hnd::env_int("HND_THIN_WGRAD", 1) == 0 || d.kh != 2 || d.kw != 2 || d.stride != 1 || d.groups > 1 || (d.pad != 0 && d.pad != 1)) return false;
   if (d.oh != d.h + 2 * d.pad - 1 || d.ow != d.w_ + 2 * d.pad - 1) return false;
   if (d.cin == 64 && d.cin_real == 64 && d.cout <= 4 && d.ldy == 4) { thick_is_x = true; return true; }
   if (d.cin == 4 && d.cout == 64 && d.ldy == 64) { thick_is_x = false; return true; }
@@ -414,6 +416,28 @@ size_t wgrad_ring_workspace(const hnd_wgrad_desc& d);
 int launch_wgrad_ring(const hnd_wgrad_desc& d, int& splits, int& co_pad, int& ncols_pad, hipStream_t stream);
 }  // namespace hnd
 
+namespace {
+
+// The partial-sum kernel of a weight gradient, decided once for hnd_conv2d_wgrad and hnd_conv2d_wgrad_variant (whose codes
+// these are).
+enum WgradKernel { WG_STAGED = 0, WG_STEM7 = 1, WG_THIN = 2, WG_RING = 3 };
+struct WgradPick {
+  WgradKernel kernel;
+  bool thick_is_x;      // WG_THIN: which operand has the 64 channels
+};
+
+WgradPick pick_wgrad(const hnd_wgrad_desc& d) {
+  bool tx = false;
+  if (hnd::stem7_wgrad_applies(d)) return {WG_STEM7, false};
+  if (thin_wgrad_applies(d, tx)) return {WG_THIN, tx};
+  if (hnd::wgrad_ring_applies(d)) return {WG_RING, false};
+  return {WG_STAGED, false};
+}
+
+}  // namespace
+
+// The MAXIMUM over every kernel that applies, not the picked kernel's need: the staged kernel's slabs are always counted and
+// the switches are read per call, so a workspace sized under one switch setting also serves the launch made under another.
 extern "C" size_t hnd_conv2d_wgrad_workspace(const hnd_wgrad_desc* desc) {
   if (!desc) return 0;
   WgradArgs a;
@@ -421,32 +445,16 @@ extern "C" size_t hnd_conv2d_wgrad_workspace(const hnd_wgrad_desc* desc) {
   if (d.cin <= 0 || d.cout <= 0 || d.kh <= 0 || d.kw <= 0 || d.oh <= 0 || d.ow <= 0 || d.n <= 0) return 0;
   plan(d, a, wgrad_bk());
   size_t need = (size_t)(d.groups > 1 ? d.groups : 1) * a.d.splitk * a.co_pad * a.ncols_pad * sizeof(float);
-  if (hnd::stem7_wgrad_applies(d)) {                    // one [64][ncols_pad] slab per persistent workgroup
-    const size_t stem = (size_t)hnd::stem7_wgrad_blocks(d) * 64 * a.ncols_pad * sizeof(float);
-    if (stem > need) need = stem;
-  }
-  if (hnd::wgrad_ring_applies(d)) {                     // one [cout][cols] slab per workgroup of the ring kernel
-    const size_t ring = hnd::wgrad_ring_workspace(d);
-    if (ring > need) need = ring;
-  }
+  // stem7: one [64][ncols_pad] slab per persistent workgroup; ring: one [cout][cols] slab per workgroup; thin: 4 KB per block
+  if (hnd::stem7_wgrad_applies(d)) need = std::max(need, (size_t)hnd::stem7_wgrad_blocks(d) * 64 * a.ncols_pad * sizeof(float));
+  if (hnd::wgrad_ring_applies(d)) need = std::max(need, hnd::wgrad_ring_workspace(d));
   bool tx;
-  if (thin_wgrad_applies(d, tx)) {                      // one 4 KB partial per block
-    int per_block;
-    const size_t thin = (size_t)thin_wgrad_blocks(d, tx, per_block) * 1024 * sizeof(float);
-    if (thin > need) need = thin;
-  }
+  int per_block;
+  if (thin_wgrad_applies(d, tx)) need = std::max(need, (size_t)thin_wgrad_blocks(d, tx, per_block) * 1024 * sizeof(float));
   return need;
 }
 
-extern "C" int hnd_conv2d_wgrad_variant(const hnd_wgrad_desc* desc) {
-  if (!desc) return -1;
-  const hnd_wgrad_desc& d = *desc;
-  bool tx;
-  if (hnd::stem7_wgrad_applies(d)) return 1;
-  if (thin_wgrad_applies(d, tx)) return 2;
-  if (hnd::wgrad_ring_applies(d)) return 3;
-  return 0;
-}
+extern "C" int hnd_conv2d_wgrad_variant(const hnd_wgrad_desc* desc) { return desc ? (int)pick_wgrad(*desc).kernel : -1; }
 
 extern "C" int hnd_conv2d_wgrad(const hnd_wgrad_desc* desc, void* stream) {
   HND_REQUIRE(desc != nullptr, "hnd_conv2d_wgrad: null descriptor");
@@ -461,57 +469,56 @@ extern "C" int hnd_conv2d_wgrad(const hnd_wgrad_desc* desc, void* stream) {
   HND_REQUIRE((long long)d.n * d.oh * d.ow < (1ll << 31) && (long long)d.n * d.h * d.w_ < (1ll << 31),
               "hnd_conv2d_wgrad: pixel count exceeds int32");
   WgradArgs a;
-  const int bk = wgrad_bk();
-  const int bmw = plan(d, a, bk);
+  const int bmw = plan(d, a, wgrad_bk());
   hipStream_t s = hnd::as_stream(stream);
   const int groups = d.groups > 1 ? d.groups : 1;
   HND_REQUIRE(groups == 1 || (d.x_group_stride > 0 && d.dy_group_stride > 0 && d.dw_group_stride > 0),
               "hnd_conv2d_wgrad: group strides must be positive when groups > 1");
-  if (hnd::stem7_wgrad_applies(d)) {
-    int rc = hnd::launch_stem7_wgrad(d, a.ncols_pad, s);
-    if (rc) return rc;
-    const int total = d.cout * d.kh * d.kw * d.cin_real;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64, 1), dim3(256), 0, s, d.slabs, d.dw,
-                       hnd::stem7_wgrad_blocks(d), 64, a.ncols_pad, d.cout, d.cin, d.cin_real, d.kh, d.kw, 0ll);
-    return hnd::check_launch("hnd_conv2d_wgrad(stem7 reduce)");
+  // the partial sums: `splits` slabs of [co_pad][ncols_pad] per group (rgroups of them, group_stride apart in dw) ...
+  const WgradPick p = pick_wgrad(d);
+  int splits = 0, co_pad = 0, ncols_pad = 0, rgroups = groups, rc;
+  long long group_stride = (long long)d.dw_group_stride;
+  const char* reduce = "hnd_conv2d_wgrad(reduce)";
+  switch (p.kernel) {
+    case WG_STEM7:
+      rc = hnd::launch_stem7_wgrad(d, a.ncols_pad, s);
+      splits = hnd::stem7_wgrad_blocks(d); co_pad = 64; ncols_pad = a.ncols_pad; rgroups = 1; group_stride = 0;
+      reduce = "hnd_conv2d_wgrad(stem7 reduce)";
+      break;
+    case WG_THIN: {
+      const bool thick_is_x = p.thick_is_x;
+      ThinWgradArgs t;
+      t.d = d;
+      t.th = thick_is_x ? d.h : d.oh; t.tw = thick_is_x ? d.w_ : d.ow;
+      t.nh = thick_is_x ? d.oh : d.h; t.nw = thick_is_x ? d.ow : d.w_;
+      t.div_w = hnd::make_fastdiv((unsigned)t.tw);
+      t.div_h = hnd::make_fastdiv((unsigned)t.th);
+      t.P = (long long)d.n * t.th * t.tw;
+      splits = thin_wgrad_blocks(d, thick_is_x, t.per_block);
+      if (thick_is_x) hipLaunchKernelGGL(thin_wgrad_kernel<true>, dim3(splits), dim3(256), 0, s, t);
+      else hipLaunchKernelGGL(thin_wgrad_kernel<false>, dim3(splits), dim3(256), 0, s, t);
+      rc = hnd::check_launch("hnd_conv2d_wgrad(thin)");
+      co_pad = thick_is_x ? 4 : 64; ncols_pad = thick_is_x ? 256 : 16; rgroups = 1; group_stride = 0;
+      reduce = "hnd_conv2d_wgrad(thin reduce)";
+      break;
+    }
+    case WG_RING:
+      rc = hnd::launch_wgrad_ring(d, splits, co_pad, ncols_pad, s);
+      reduce = "hnd_conv2d_wgrad(ring reduce)";
+      break;
+    default: {
+      const dim3 grid(a.rtiles * a.ctiles * a.d.splitk, groups);
+      constexpr size_t lds128 = wgrad_lds_bytes<128, 16>(), lds64 = wgrad_lds_bytes<64, 16>();
+      if (bmw == 128) hipLaunchKernelGGL((wgrad_kernel<128, 16>), grid, dim3(256), lds128, s, a);
+      else hipLaunchKernelGGL((wgrad_kernel<64, 16>), grid, dim3(256), lds64, s, a);
+      rc = hnd::check_launch("hnd_conv2d_wgrad");
+      splits = a.d.splitk; co_pad = a.co_pad; ncols_pad = a.ncols_pad;
+    }
   }
-  bool thick_is_x;
-  if (thin_wgrad_applies(d, thick_is_x)) {
-    ThinWgradArgs t;
-    t.d = d;
-    t.th = thick_is_x ? d.h : d.oh; t.tw = thick_is_x ? d.w_ : d.ow;
-    t.nh = thick_is_x ? d.oh : d.h; t.nw = thick_is_x ? d.ow : d.w_;
-    t.div_w = hnd::make_fastdiv((unsigned)t.tw);
-    t.div_h = hnd::make_fastdiv((unsigned)t.th);
-    t.P = (long long)d.n * t.th * t.tw;
-    const int blocks = thin_wgrad_blocks(d, thick_is_x, t.per_block);
-    if (thick_is_x) hipLaunchKernelGGL(thin_wgrad_kernel<true>, dim3(blocks), dim3(256), 0, s, t);
-    else hipLaunchKernelGGL(thin_wgrad_kernel<false>, dim3(blocks), dim3(256), 0, s, t);
-    int rc = hnd::check_launch("hnd_conv2d_wgrad(thin)");
-    if (rc) return rc;
-    const int total = d.cout * d.kh * d.kw * d.cin_real;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64, 1), dim3(256), 0, s, d.slabs, d.dw, blocks,
-                       thick_is_x ? 4 : 64, thick_is_x ? 256 : 16, d.cout, d.cin, d.cin_real, d.kh, d.kw, 0ll);
-    return hnd::check_launch("hnd_conv2d_wgrad(thin reduce)");
-  }
-  if (hnd::wgrad_ring_applies(d)) {
-    int splits = 0, co_pad = 0, ncols_pad = 0;
-    int rc = hnd::launch_wgrad_ring(d, splits, co_pad, ncols_pad, s);
-    if (rc) return rc;
-    const int total = d.cout * d.kh * d.kw * d.cin_real;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64, groups), dim3(256), 0, s, d.slabs, d.dw, splits,
-                       co_pad, ncols_pad, d.cout, d.cin, d.cin_real, d.kh, d.kw, (long long)d.dw_group_stride);
-    return hnd::check_launch("hnd_conv2d_wgrad(ring reduce)");
-  }
-  const dim3 grid(a.rtiles * a.ctiles * a.d.splitk, groups);
-  constexpr size_t lds128 = wgrad_lds_bytes<128, 16>(), lds64 = wgrad_lds_bytes<64, 16>();
-  if (bmw == 128) hipLaunchKernelGGL((wgrad_kernel<128, 16>), grid, dim3(256), lds128, s, a);
-  else hipLaunchKernelGGL((wgrad_kernel<64, 16>), grid, dim3(256), lds64, s, a);
-  int rc = hnd::check_launch("hnd_conv2d_wgrad");
   if (rc) return rc;
+  // ... and their sum, in slab order, into dw
   const int total = d.cout * d.kh * d.kw * d.cin_real;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64, groups), dim3(256), 0, s, d.slabs, d.dw,
-                     a.d.splitk, a.co_pad, a.ncols_pad, d.cout, d.cin, d.cin_real, d.kh, d.kw,
-                     (long long)d.dw_group_stride);
-  return hnd::check_launch("hnd_conv2d_wgrad(reduce)");
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((total + 63) / 64, rgroups), dim3(256), 0, s, d.slabs, d.dw, splits, co_pad,
+                     ncols_pad, d.cout, d.cin, d.cin_real, d.kh, d.kw, group_stride);
+  return hnd::check_launch(reduce);
 }

@@ -28,7 +28,6 @@
 
 #include <stdlib.h>
 
-#include <atomic>
 
 namespace {
 
@@ -284,6 +283,11 @@ int launch_narrow(const WringArgs& a, dim3 grid, hipStream_t s) {
   return hnd::check_launch("hnd_conv2d_wgrad(ring, 64 columns)");
 }
 
+// the tap form: anything but a dense 1x1 (stride 1, no padding)
+bool wring_taps(const hnd_wgrad_desc& d) { return d.kh * d.kw > 1 || d.pad != 0 || d.stride != 1; }
+// 64 columns (cin = 64, 1x1 / grouped): the 4 x 1 wave arrangement (launch_narrow)
+bool wring_narrow(const hnd_wgrad_desc& d) { return !wring_taps(d) && d.cin == 64 && d.cout % 256 == 0; }
+
 }  // namespace
 
 namespace hnd {
@@ -296,14 +300,11 @@ bool wgrad_ring_applies(const hnd_wgrad_desc& d) {
   // 1x1 (grouped Winograd-domain) form only -- in the step the tap form of the head's direct 2x2 convs is no faster than
   // the staged kernel (conv1 1.37 vs 1.31 ms, conv5 0.74 vs 0.69 ms, profiles/r04_per_launch_events*.txt; in isolation
   // it wins by 5-7 %, tools/bench_wgrad.py): its ~100 vector instructions per k-step are not hidden yet.
-  const char* e = getenv("HND_WGRAD_RING");
-  if (e && atoi(e) == 0) return false;
-  const int mode = hnd::debug_picker("wgrad_ring_taps") > 0 ? 2 : 1;
-  if (mode != 2 && (d.kh * d.kw > 1 || d.pad != 0 || d.stride != 1)) return false;
+  if (env_int("HND_WGRAD_RING", 1) == 0) return false;
+  const bool taps = wring_taps(d);
+  if (taps && debug_picker("wgrad_ring_taps") <= 0) return false;
   if (d.cout % 128 != 0 || d.cin % 64 != 0 || d.cin_real != d.cin || d.ldy % 4 != 0 || d.ldy < d.cout) return false;
-  const bool taps = d.kh * d.kw > 1 || d.pad != 0 || d.stride != 1;
-  const bool narrow = !taps && d.cin == 64 && d.cout % 256 == 0;      // 64 columns: the 4 x 1 wave arrangement
-  if ((d.kh * d.kw * d.cin) % 128 != 0 && !narrow) return false;
+  if ((d.kh * d.kw * d.cin) % 128 != 0 && !wring_narrow(d)) return false;
   if (!taps && (d.oh != d.h || d.ow != d.w_)) return false;
   if (!taps && d.pro_scale) return false;               // (the prologue lives on the tap path)
   if (taps && d.ow < 4) return false;                   // (a k-step of 4 pixels wraps at most one row)
@@ -312,17 +313,12 @@ bool wgrad_ring_applies(const hnd_wgrad_desc& d) {
   return true;
 }
 
-static bool wring_narrow(const hnd_wgrad_desc& d) {
-  return d.kh * d.kw == 1 && d.pad == 0 && d.stride == 1 && d.cin == 64 && d.cout % 256 == 0;
-}
-
 static void wring_plan(const hnd_wgrad_desc& d, WringArgs& a, int& ah, int& bh) {
   a.d = d;
   a.M = d.n * d.oh * d.ow;
   const int ncols = d.kh * d.kw * d.cin;
-  const bool taps = d.kh * d.kw > 1 || d.pad != 0 || d.stride != 1;
   const bool narrow = wring_narrow(d);
-  const bool small = (taps && taps_small(d)) || narrow;     // 64 x 64 wave tiles, two waves per SIMD
+  const bool small = (wring_taps(d) && taps_small(d)) || narrow;     // 64 x 64 wave tiles, two waves per SIMD
   ah = (d.cout % 256 == 0 && !small) ? 2 : 1;
   bh = (ncols % 256 == 0 && !small) ? 2 : 1;
   a.rtiles = narrow ? d.cout / 256 : d.cout / (128 * ah);
@@ -358,7 +354,7 @@ int launch_wgrad_ring(const hnd_wgrad_desc& d, int& splits, int& co_pad, int& nc
   splits = a.splits;
   co_pad = a.co_pad;
   ncols_pad = a.ncols_pad;
-  const bool taps = d.kh * d.kw > 1 || d.pad != 0 || d.stride != 1;
+  const bool taps = wring_taps(d);
   const dim3 grid(a.rtiles * a.ctiles * a.splits, d.groups > 1 ? d.groups : 1);
   if (wring_narrow(d)) return launch_narrow(a, grid, s);
   if (ah == 2) return bh == 2 ? launch_ab<2, 2>(a, taps, grid, s) : launch_ab<2, 1>(a, taps, grid, s);

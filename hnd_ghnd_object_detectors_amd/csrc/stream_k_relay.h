@@ -29,9 +29,8 @@ namespace hnd {
 // ---- host side
 // tiles of a launch with `wn` wave columns (block tile 64 * 4 / wn x 64 * wn) and the persistent grid
 inline void relay_grid(const hnd_conv_desc& d, int wn, int& mtiles, int& ntiles, int& grid) {
-  const long long M = (long long)d.n * d.oh * d.ow;
   const int bm = 64 * (4 / wn), bn = 64 * wn;
-  mtiles = (int)((M + bm - 1) / bm);
+  mtiles = (int)((gemm_rows(d) + bm - 1) / bm);
   ntiles = d.cout / bn;
   grid = (cu_count() / 8) * 8;
 }

@@ -1,6 +1,6 @@
 """Worker of tests/test_ops_gpu.py::test_thin_n_kernel_is_bit_identical_to_the_mfma_path: runs the cout <= 4 launches
 and two whole distillation steps in THIS process' mode (HND_THIN_N=0: MFMA tiles, 1: vector-ALU kernel; the library reads
-the switch once) and saves every result for a bit-for-bit comparison.
+the switch at every launch, like the others) and saves every result for a bit-for-bit comparison.
 usage: HND_THIN_N=<0|1> python tests/thin_worker.py <out.pt>"""
 import os
 import sys
