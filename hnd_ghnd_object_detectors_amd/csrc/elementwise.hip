@@ -838,6 +838,191 @@ __global__ void mimic_finalize_kernel(const MimicArgs a, const double* __restric
   }
 }
 
+// Terms that share a student tensor (pairs of one call with the same `grad`): a GROUP of m members.  The group's
+// workgroups walk the tensor as mimic_chunks does, read the student once and every teacher once, form each member's value
+// and gradient, add the gradients in fp32 in increasing pair index, mask the SUM once and store it once.
+// The criterion of a member is not a template parameter here (m members of 4 kinds would be 4^m loops): all four kinds are
+// the two-zone form  quad ? (vq d d, gq d) : (fma(vl, |d|, vc), gl sign(d))  with per-member constants that are fixed
+// before the chunk loop -- MSE is all-quadratic (vq = 1), L1 all-linear (thr = 0, vl = 1, vc = 0), Huber's `<=` is `<` of
+// the next float up.  Both arms are locals computed unconditionally and then selected, as in MimicOp, and the arithmetic
+// of each arm is MimicOp's own, so a member's value and gradient are the ones its lone launch forms.
+struct MimicGroupArgs {
+  MimicDev pair[kMaxPairs];             // in UNIT order: the members of a group are neighbours, in increasing pair index
+  int unit_first_block[kMaxPairs + 1];
+  int unit_first_pair[kMaxPairs + 1];
+  int slot_first[kMaxPairs];            // the partial sums of pair[j] are scratch[slot_first[j] .. + its unit's blocks)
+  int slot_count[kMaxPairs];
+  int out_index[kMaxPairs];             // pair[j] is pairs[out_index[j]] of the call
+  int tsrc[kMaxPairs];                  // index within its stage of the member whose teacher registers pair[j] uses (its own, or
+                                        // an earlier one's with the same teacher pointer)
+  int nunits, npairs;
+};
+
+struct MimicMember {
+  const float* teacher;
+  float thr, vq, vl, vc, gq, gl;
+  bool allq;
+};
+
+__device__ __forceinline__ MimicMember mimic_member(const MimicDev& P) {
+  MimicMember m;
+  m.teacher = P.teacher;
+  m.allq = P.kind == HND_MIMIC_MSE;
+  m.thr = P.kind == HND_MIMIC_HUBER ? nextafterf(P.thr, INFINITY) : (P.kind == HND_MIMIC_SMOOTH_L1 ? P.thr : 0.f);
+  m.vq = P.kind == HND_MIMIC_MSE ? 1.f : P.vq;
+  m.vl = P.kind == HND_MIMIC_L1 ? 1.f : P.vl;
+  m.vc = P.vc;
+  m.gq = P.gq;
+  m.gl = P.gl;
+  return m;
+}
+
+__device__ __forceinline__ void mimic_any1(float d, const MimicMember& k, float& v, float& g) {
+  const float ad = fabsf(d);
+  const bool quad = k.allq | (ad < k.thr);
+  const float vquad = k.vq * d * d, vlin = fmaf(k.vl, ad, k.vc);
+  const float signed_gl = copysignf(k.gl, d);
+  const float gquad = k.gq * d, glin = d != 0.f ? signed_gl : 0.f;
+  v = quad ? vquad : vlin;
+  g = quad ? gquad : glin;
+}
+
+// The members of a group are taken in stages of kStage: the loads of a stage (and, in the first, the student's) are all
+// issued before the first use, so a group of 2 or 3 has 12 or 16 vector loads in flight per thread where a lone pair has 8,
+// and a larger group never holds more than kStage teachers.  The gradient sum so far and the student stay in registers
+// between stages.  The stage loop is unrolled with a workgroup-uniform `member exists` test around each member, so every
+// register index is a constant; a member whose teacher an earlier member of its stage has loaded (tsrc) takes that member's
+// registers -- a select on a uniform condition -- instead of loading again.
+constexpr int kStage = 3;
+
+__device__ __forceinline__ void mimic_group_chunks(const MimicGroupArgs& a, int p0, int m, int nb, int lb, double* scratch,
+                                                   double (*wsum)[4]) {
+  const float* student = a.pair[p0].student;
+  float* grad = a.pair[p0].grad;
+  const int relu_mask = a.pair[p0].relu_mask;
+  const long long n4 = a.pair[p0].numel >> 2;
+  float acc[kMaxPairs];
+#pragma unroll
+  for (int i = 0; i < kMaxPairs; ++i) acc[i] = 0.f;
+  const long long chunk = 256ll * kEwU;
+  for (long long base = (long long)lb * chunk + threadIdx.x; base < n4; base += (long long)nb * chunk) {
+    f32x4 sv[kEwU], gs[kEwU];
+#pragma unroll
+    for (int u = 0; u < kEwU; ++u) {
+      const long long e = base + 256ll * u;
+      if (e < n4) sv[u] = *(const f32x4*)(student + e * 4);
+    }
+#pragma unroll
+    for (int st = 0; st < kMaxPairs; st += kStage) {
+      if (st >= m) break;
+      f32x4 tv[kStage][kEwU];
+#pragma unroll
+      for (int j = 0; j < kStage; ++j) {
+        if (st + j >= kMaxPairs || st + j >= m || a.tsrc[p0 + st + j] != j) continue;
+        const float* teacher = a.pair[p0 + st + j].teacher;
+#pragma unroll
+        for (int u = 0; u < kEwU; ++u) {
+          const long long e = base + 256ll * u;
+          if (e < n4) tv[j][u] = *(const f32x4*)(teacher + e * 4);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < kStage; ++j) {
+        if (st + j >= kMaxPairs || st + j >= m) continue;
+        const MimicMember mem = mimic_member(a.pair[p0 + st + j]);
+        const int src = a.tsrc[p0 + st + j];
+#pragma unroll
+        for (int u = 0; u < kEwU; ++u) {
+          if (base + 256ll * u >= n4) continue;
+          f32x4 t = tv[j][u];
+#pragma unroll
+          for (int q = 0; q < j; ++q) t = src == q ? tv[q][u] : t;
+          const f32x4 df = sv[u] - t;
+          float vx, vy, vz, vw, gx, gy, gz, gw;
+          mimic_any1(df.x, mem, vx, gx); mimic_any1(df.y, mem, vy, gy);
+          mimic_any1(df.z, mem, vz, gz); mimic_any1(df.w, mem, vw, gw);
+          f32x4 g;
+          g.x = gx; g.y = gy; g.z = gz; g.w = gw;
+          acc[st + j] += (vx + vy) + (vz + vw);
+          gs[u] = (st + j == 0) ? g : gs[u] + g;          // fp32, in increasing pair index
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < kEwU; ++u) {
+      const long long e = base + 256ll * u;
+      if (e >= n4) continue;
+      f32x4 gg = gs[u];
+      const f32x4 s = sv[u];
+      if (relu_mask) {          // the mask, once, on the sum
+        gg.x = s.x > 0.f ? gg.x : 0.f; gg.y = s.y > 0.f ? gg.y : 0.f;
+        gg.z = s.z > 0.f ? gg.z : 0.f; gg.w = s.w > 0.f ? gg.w : 0.f;
+      }
+      *(f32x4*)(grad + e * 4) = gg;
+    }
+  }
+  // per member: the thread's sum, then the wave, then the four waves -- mimic_kernel's order; one slot per (member,
+  // workgroup), written by nobody else
+#pragma unroll
+  for (int i = 0; i < kMaxPairs; ++i) {
+    if (i >= m) break;
+    const double dsum = wave_sum_d((double)acc[i]);
+    if ((threadIdx.x & 63) == 0) wsum[i][threadIdx.x >> 6] = dsum;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < m) {
+    const int i = threadIdx.x;
+    scratch[a.slot_first[p0 + i] + lb] = (wsum[i][0] + wsum[i][1]) + (wsum[i][2] + wsum[i][3]);
+  }
+}
+
+__global__ void __launch_bounds__(256) mimic_group_kernel(const MimicGroupArgs a, double* __restrict__ scratch) {
+  __shared__ double wsum[kMaxPairs][4];
+  int un = 0;
+  while (un + 1 < a.nunits && (int)blockIdx.x >= a.unit_first_block[un + 1]) ++un;
+  const int nb = a.unit_first_block[un + 1] - a.unit_first_block[un], lb = blockIdx.x - a.unit_first_block[un];
+  const int p0 = a.unit_first_pair[un], m = a.unit_first_pair[un + 1] - p0;
+  if (m == 1) {                 // a lone pair: mimic_kernel's own path
+    const MimicDev P = a.pair[p0];
+    float acc;
+    switch (P.kind) {
+      case HND_MIMIC_L1: acc = mimic_chunks<HND_MIMIC_L1>(P, nb, lb); break;
+      case HND_MIMIC_SMOOTH_L1: acc = mimic_chunks<HND_MIMIC_SMOOTH_L1>(P, nb, lb); break;
+      case HND_MIMIC_HUBER: acc = mimic_chunks<HND_MIMIC_HUBER>(P, nb, lb); break;
+      default: acc = mimic_chunks<HND_MIMIC_MSE>(P, nb, lb); break;
+    }
+    double dsum = wave_sum_d((double)acc);
+    if ((threadIdx.x & 63) == 0) wsum[0][threadIdx.x >> 6] = dsum;
+    __syncthreads();
+    if (threadIdx.x == 0) scratch[a.slot_first[p0] + lb] = (wsum[0][0] + wsum[0][1]) + (wsum[0][2] + wsum[0][3]);
+    return;
+  }
+  mimic_group_chunks(a, p0, m, nb, lb, scratch, wsum);
+}
+
+__global__ void mimic_group_finalize_kernel(const MimicGroupArgs a, const double* __restrict__ scratch,
+                                            double* __restrict__ out) {
+  __shared__ double term[kMaxPairs];
+  const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (j < a.npairs) {
+    double s = 0.0;
+    for (int b = a.slot_first[j] + lane; b < a.slot_first[j] + a.slot_count[j]; b += 64) s += scratch[b];
+    s = wave_sum_d(s);
+    if (lane == 0) {
+      double t = s * a.pair[j].term_scale;
+      if (a.pair[j].term_div != 0.0) t /= a.pair[j].term_div;
+      term[a.out_index[j]] = t;
+      out[1 + a.out_index[j]] = t;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {       // (the total in the order of the call's pairs)
+    double tot = 0.0;
+    for (int i = 0; i < a.npairs; ++i) tot += term[i];
+    out[0] = tot;
+  }
+}
+
 __global__ void scale_by_scalar_kernel(float* x, long long n, const float* s) {
   const float f = *s;
   if (f == 1.0f) return;
@@ -1260,7 +1445,8 @@ int hnd_bn_bwd_apply(const float* g, const float* x, const float* scale, const f
   return hnd::check_launch("hnd_bn_bwd_apply");
 }
 
-size_t hnd_mse_scratch_elems(void) { return kMseBlocks; }
+// (a loss launch has at most kMseBlocks workgroups; each writes one partial sum, or one per member of its group)
+size_t hnd_mse_scratch_elems(void) { return (size_t)kMseBlocks * kMaxPairs; }
 
 int hnd_mse_sum_fwd_bwd(const hnd_mse_pair* pairs, int npairs, double* loss_out, double* scratch, void* stream) {
   HND_REQUIRE(pairs && loss_out && scratch, "hnd_mse_sum_fwd_bwd: null pointer");
@@ -1281,6 +1467,62 @@ int hnd_mse_sum_fwd_bwd(const hnd_mse_pair* pairs, int npairs, double* loss_out,
   if (rc) return rc;
   hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(64 * kMaxPairs), 0, s, a, scratch, loss_out);
   return hnd::check_launch("hnd_mse_sum_fwd_bwd(finalize)");
+}
+
+// A call with at least one group.  Units = groups and lone pairs, in the order of their first pair; a unit's workgroups
+// follow its share of the traffic (numel * 3 for a lone pair, numel * (m + 2) for a group of m), and every member of a
+// unit has one scratch slot per workgroup of the unit, so the slots of a call stay within kMseBlocks * kMaxPairs.
+static int mimic_launch_grouped(const MimicArgs& a, const hnd_mimic_pair* pairs, void* stream, double* scratch,
+                                double* loss_out) {
+  const int npairs = a.npairs;
+  MimicGroupArgs g;
+  g.npairs = npairs;
+  int nunits = 0, placed = 0;
+  bool done[kMaxPairs] = {};
+  long long weight[kMaxPairs], total = 0;
+  for (int i = 0; i < npairs; ++i) {
+    if (done[i]) continue;
+    g.unit_first_pair[nunits] = placed;
+    for (int j = i; j < npairs; ++j) {
+      if (j != i && !(pairs[i].grad && pairs[j].grad == pairs[i].grad)) continue;
+      done[j] = true;
+      const int at = placed - g.unit_first_pair[nunits];       // member index within the group
+      g.pair[placed] = a.pair[j];
+      g.out_index[placed] = j;
+      g.tsrc[placed] = at % kStage;
+      for (int e = placed - at % kStage; e < placed; ++e)      // an earlier member of the same stage
+        if (g.pair[e].teacher == g.pair[placed].teacher) { g.tsrc[placed] = (e - g.unit_first_pair[nunits]) % kStage; break; }
+      ++placed;
+    }
+    const int m = placed - g.unit_first_pair[nunits];
+    weight[nunits] = pairs[i].numel * (m == 1 ? 3 : m + 2);
+    total += weight[nunits];
+    ++nunits;
+  }
+  g.unit_first_pair[nunits] = placed;
+  g.nunits = nunits;
+  int used = 0, slots = 0;
+  for (int u = 0; u < nunits; ++u) {
+    const int p0 = g.unit_first_pair[u], m = g.unit_first_pair[u + 1] - p0;
+    g.unit_first_block[u] = used;
+    long long nb = (long long)(kMseBlocks - nunits) * weight[u] / total + 1;
+    const long long maxb = (g.pair[p0].numel / 4 + 256 * kEwU - 1) / (256 * kEwU);
+    if (nb > maxb) nb = maxb;
+    if (nb < 1) nb = 1;
+    used += (int)nb;
+    for (int i = 0; i < m; ++i) {
+      g.slot_first[p0 + i] = slots;
+      g.slot_count[p0 + i] = (int)nb;
+      slots += (int)nb;
+    }
+  }
+  g.unit_first_block[nunits] = used;
+  hipStream_t s = hnd::as_stream(stream);
+  hipLaunchKernelGGL(mimic_group_kernel, dim3(used), dim3(256), 0, s, g, scratch);
+  int rc = hnd::check_launch("hnd_mimic_loss_fwd_bwd(grouped)");
+  if (rc) return rc;
+  hipLaunchKernelGGL(mimic_group_finalize_kernel, dim3(1), dim3(64 * kMaxPairs), 0, s, g, scratch, loss_out);
+  return hnd::check_launch("hnd_mimic_loss_fwd_bwd(grouped finalize)");
 }
 
 int hnd_mimic_loss_fwd_bwd(const hnd_mimic_pair* pairs, int npairs, double* loss_out, double* scratch, void* stream) {
@@ -1328,6 +1570,25 @@ int hnd_mimic_loss_fwd_bwd(const hnd_mimic_pair* pairs, int npairs, double* loss
                 "hnd_mimic_loss_fwd_bwd: pair %d: factor / count / beta / delta give a weight outside fp32", k);
     total += p.numel;
   }
+  // pairs that share `grad` form a group; any other overlap of two gradient ranges is a race.  (Pointer comparisons only.)
+  bool grouped = false;
+  for (int i = 0; i < npairs; ++i) {
+    for (int j = i + 1; j < npairs; ++j) {
+      const hnd_mimic_pair &p = pairs[i], &q = pairs[j];
+      if (!p.grad || !q.grad) continue;
+      if (p.grad == q.grad) {
+        HND_REQUIRE(p.student == q.student && p.numel == q.numel && (p.relu_mask != 0) == (q.relu_mask != 0),
+                    "hnd_mimic_loss_fwd_bwd: pairs %d and %d share grad, so they must have the same student, numel and "
+                    "relu_mask", i, j);
+        grouped = true;
+        continue;
+      }
+      const uintptr_t pb = (uintptr_t)p.grad, qb = (uintptr_t)q.grad;
+      HND_REQUIRE(pb + (uintptr_t)p.numel * 4 <= qb || qb + (uintptr_t)q.numel * 4 <= pb,
+                  "hnd_mimic_loss_fwd_bwd: the grad ranges of pairs %d and %d overlap without being identical", i, j);
+    }
+  }
+  if (grouped) return mimic_launch_grouped(a, pairs, stream, scratch, loss_out);
   const int used = loss_split_blocks(pairs, npairs, total, a.first_block);
   hipStream_t s = hnd::as_stream(stream);
   hipLaunchKernelGGL(mimic_kernel, dim3(used), dim3(256), 0, s, a, scratch);

@@ -242,7 +242,7 @@ def distill_loss(terms):
             raise NotImplementedError('a pyramid term together with a term on an inner Bottleneck of layer4 is not built')
         top = ('layer4', None)
     pairs, loss_grads, block_grads, grad_bufs = [], {}, {}, []
-    fpn_grads, fpn_state, enc_seen = {}, [None], [False]
+    fpn_grads, fpn_state, enc_grad = {}, [None], [None]
     for (tname, t_out, s_out, factor), p in zip(terms, pos):
         t_buf, s_buf = to_nhwc(t_out), to_nhwc(s_out)
         if tuple(t_buf.shape) != tuple(s_buf.shape):
@@ -251,18 +251,15 @@ def distill_loss(terms):
         grad = None
         if trainable and p[0] == 'fpn':
             fpn_eng = srcs[pos.index(p)][4]
-            if p[1] in fpn_grads:
-                raise NotImplementedError('two loss terms on pyramid map %d' % p[1])
-            grad = fpn_grads[p[1]] = fpn_eng.term_grad_buffer(p[1])
+            if p[1] not in fpn_grads:
+                fpn_grads[p[1]] = fpn_eng.term_grad_buffer(p[1])
+            grad = fpn_grads[p[1]]
             fpn_state[0] = fpn_eng
-            grad_bufs.append(grad)
         elif trainable and p[1] == 'encoder':
             head = body.layer_engine('layer1')
-            if enc_seen[0]:
-                raise NotImplementedError('two loss terms on the bottleneck tensor')
-            enc_seen[0] = True
-            grad = head.enc_grad_buffer(top=(p == top))
-            grad_bufs.append(grad)
+            if enc_grad[0] is None:
+                enc_grad[0] = head.enc_grad_buffer(top=(p == top))
+            grad = enc_grad[0]
         elif trainable:
             lname, blk = p
             eng = body.layer_engine(lname)          # its own engine, or the SharedTrunk's (engine.SharedTrunk)
@@ -270,26 +267,23 @@ def distill_loss(terms):
                 # masked by the producing ReLU in the same pass
                 grad = eng.grad_out_buffer(blk) if blk is not None else eng.grad_out_buffer()
             elif blk is None:
-                grad = eng.bufs.get('loss_grad', s_buf.shape)
-                if lname in loss_grads:
-                    raise NotImplementedError('two loss terms on the output of %s' % lname)
-                loss_grads[lname] = grad
+                grad = loss_grads[lname] = eng.bufs.get('loss_grad', s_buf.shape)
             else:
-                grad = eng.bufs.get('loss_grad_blk%d' % blk, s_buf.shape)
-                if blk in block_grads.setdefault(lname, {}):
-                    raise NotImplementedError('two loss terms on the output of %s.%d' % (lname, blk))
-                block_grads[lname][blk] = grad
+                grad = block_grads.setdefault(lname, {})[blk] = eng.bufs.get('loss_grad_blk%d' % blk, s_buf.shape)
+        # terms at one position share that position's gradient buffer (the launch adds their gradients and stores the sum
+        # once); the buffer enters grad_bufs ONCE -- backward scales every entry by autograd's grad_output
+        if grad is not None and not any(g.data_ptr() == grad.data_ptr() for g in grad_bufs):
             grad_bufs.append(grad)
         # (masked by the producing ReLU only where the tensor IS a ReLU output that starts the backward: layer outputs /
         # Bottleneck outputs -- not the bottleneck tensor, a raw conv output, nor a pyramid map)
         pairs.append((t_buf, s_buf, grad, float(factor), p == top and p[0] != 'fpn' and p[1] != 'encoder'))
-    if len([p for p in pos if p == top]) > 1:
-        raise NotImplementedError('two loss terms on the same (top) student tensor')
     key = tuple((p[0].data_ptr(), p[1].data_ptr(), None if p[2] is None else p[2].data_ptr(), p[3], p[4])
                 for p in pairs)
-    general = not all(c.is_mse_sum() for c in crits)
+    shared = len(set(pos)) < len(pos)
+    general = shared or not all(c.is_mse_sum() for c in crits)
     if general:
-        # any other criterion: ALL terms go through the general entry point (still one launch + one finalize).  A mean
+        # any other criterion, or two terms on one student tensor (their pairs share `grad`: a group of the general entry
+        # point): ALL terms go through the general entry point (still one launch + one finalize).  A mean
         # divides by the LOGICAL element count of the hooked tensor, not by the buffer's (padded channels)
         pairs = [p + (c.kind, c.param, s_out.numel() if c.reduction == 'mean' else 0)
                  for p, c, (_, _, s_out, _) in zip(pairs, crits, terms)]

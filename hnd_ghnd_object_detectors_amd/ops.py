@@ -652,7 +652,9 @@ class MimicLaunch(object):
 
     def __init__(self, pairs, device):
         """pairs: list of (teacher, student, grad_or_None, factor, relu_mask, kind, param, count); kind is a key of
-        _lib.MIMIC_KINDS, param the beta / delta, count the LOGICAL element count a mean divides by (0 = sum)."""
+        _lib.MIMIC_KINDS, param the beta / delta, count the LOGICAL element count a mean divides by (0 = sum).
+        Pairs that name the SAME grad tensor (and the same student) form a group: the launch reads the student once, adds
+        the gradients of the members in pair order and stores the sum once."""
         self.n = len(pairs)
         self.arr = (MimicPair * self.n)()
         self.keep = pairs
@@ -666,7 +668,11 @@ class MimicLaunch(object):
         self.scratch = torch.empty(_L.hnd_mse_scratch_elems(), dtype=torch.float64, device=device)
 
     def run(self):
-        nbytes = sum(4 * p[0].numel() * (3 if p[2] is not None else 2) for p in self.keep)
+        nbytes, grads = 0, set()
+        for p in self.keep:                 # (a group: one read of the student and one write of grad for all its members)
+            later = p[2] is not None and ptr(p[2]) in grads
+            nbytes += 4 * p[0].numel() * (1 if later else 2 if p[2] is None else 3)
+            grads.add(ptr(p[2]))
         LOSS_LAUNCHES['hnd_mimic_loss_fwd_bwd'] += 1
         _hbm('mse', nbytes, lambda: check(
             _L.hnd_mimic_loss_fwd_bwd(self.arr, self.n, ptr(self.out), ptr(self.scratch), stream_ptr()),

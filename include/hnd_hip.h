@@ -439,7 +439,19 @@ int hnd_mse_sum_fwd_bwd(const hnd_mse_pair* pairs, int npairs, double* loss_out,
  * hnd_mse_sum_fwd_bwd.  HND_ERR_INVALID before any launch: null pointers, npairs outside 1..8, numel not a positive
  * multiple of 4, unknown kind, param negative or not finite, count outside 0..numel, or factor / count / param whose
  * gradient weight (w / beta, w * delta) has no finite fp32 value.  A beta below FLT_MIN (0 included) is L1.  delta = 0 is
- * accepted here (the loss is identically 0); torch's rule delta > 0 is enforced by the Python criterion HipHuberLoss. */
+ * accepted here (the loss is identically 0); torch's rule delta > 0 is enforced by the Python criterion HipHuberLoss.
+ *
+ * Terms on one student tensor: pairs of a call whose `grad` is the SAME non-NULL pointer form a GROUP (2..8 members; any
+ * number of groups and lone pairs in one call).  The members must agree in student, numel and relu_mask and may differ
+ * in teacher, kind, param, count and factor.  The group's workgroups read the student once and every distinct teacher
+ * pointer once (within a stage of three consecutive members), and
+ *   grad = mask(sum_k g_k):  the member gradients g_k are added in fp32 in increasing pair index, the mask s > 0 is applied
+ *   once, to the sum, and every element of grad is stored once;
+ * loss_out[1 + k] stays the value of pair k and loss_out[0] the total (term scale and the mean's division in double, as
+ * for a lone pair).  Bit-reproducible; a call without a group takes the path, and gives the bits, it always had.
+ * HND_ERR_INVALID before any launch, with both pair indices in the message: two pairs that share grad and disagree in
+ * student, numel or relu_mask; two grad ranges [grad, grad + numel) that overlap without being identical (two sets of
+ * workgroups would write the same elements).  These checks compare pointers only. */
 typedef enum hnd_mimic_kind {
   HND_MIMIC_MSE = 0,
   HND_MIMIC_L1 = 1,
