@@ -1,4 +1,5 @@
-"""ctypes binding of libhnd_hip.so (C ABI declared in include/hnd_hip.h).
+"""ctypes binding of libhnd_hip.so (C ABI declared in include/hnd_hip.h; the further optimizer kinds in
+include/hnd_optim.h, with a table and a version of their own).
 
 The library is the ONLY compute path of this package: if it is missing the import of any
 compute module fails loudly (no CPU / eager fallback exists on purpose).
@@ -171,6 +172,27 @@ _SIGNATURES = {
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 
+
+# ---- include/hnd_optim.h: its own struct, enum, version and symbol table (hnd_hip.h and ABI_VERSION do not move with it)
+class OptimDesc(C.Structure):
+    """struct hnd_optim_desc"""
+    _fields_ = [(n, vp) for n in ('param', 'grad', 'state0', 'state1', 'state2')] + \
+               [('numel', C.c_int64), ('step', C.c_int64)] + \
+               [(n, C.c_double) for n in ('grad_scale', 'lr', 'weight_decay', 'eps', 'beta1', 'beta2', 'momentum',
+                                          'lr_decay')] + \
+               [(n, C.c_int32) for n in ('kind', 'amsgrad', 'centered', 'reserved')]
+
+
+OPTIM_ABI = 1
+OPTIM_KINDS = {'adam': 0, 'adagrad': 1, 'rmsprop': 2}                # enum hnd_optim_kind
+
+_OPTIM_SIGNATURES = {
+    'hnd_optim_abi': (C.c_int, []),
+    'hnd_optim_step_flat': (C.c_int, [C.POINTER(OptimDesc), vp]),
+}
+
+OPTIM_SYMBOLS = tuple(sorted(_OPTIM_SIGNATURES))
+
 _lib = None
 
 
@@ -193,7 +215,7 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in _SIGNATURES.items():
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -202,6 +224,8 @@ def load():
         fn.argtypes = args
     if lib.hnd_abi_version() != ABI_VERSION:
         raise HndLibraryError('libhnd_hip.so ABI %d != expected %d' % (lib.hnd_abi_version(), ABI_VERSION))
+    if lib.hnd_optim_abi() != OPTIM_ABI:
+        raise HndLibraryError('libhnd_hip.so optimizer ABI %d != expected %d' % (lib.hnd_optim_abi(), OPTIM_ABI))
     _lib = lib
     return lib
 

@@ -1,11 +1,11 @@
 """Factories the runner calls by name (src/mimic_runner.py:67-70, src/distillation/loss.py:13).
 
-get_optimizer('Adam' / 'SGD') returns the fused flat-arena optimizers, get_loss('MSELoss' / 'L1Loss' / 'SmoothL1Loss' /
+get_optimizer('Adam' / 'SGD' / 'Adagrad' / 'RMSprop') returns the fused flat-arena optimizers, get_loss('MSELoss' / 'L1Loss' / 'SmoothL1Loss' /
 'HuberLoss', reduction 'sum' or 'mean') a criterion of the fused HIP loss; schedulers are plain torch (host-side scalars only)."""
 import torch
 from torch import nn
 
-from ...optim import FusedAdam, FusedSGD
+from ...optim import FusedAdam, FusedSGD, FusedAdagrad, FusedRMSprop
 from ...distillation.hip_loss import HipMSELoss, HipL1Loss, HipSmoothL1Loss, HipHuberLoss, SUPPORTED_CRITERIA
 
 
@@ -15,8 +15,12 @@ def get_optimizer(target, optim_type, optim_params_config):
         return FusedAdam(params, **optim_params_config)
     if optim_type.lower() == 'sgd':
         return FusedSGD(params, **optim_params_config)
-    raise ValueError('optim_type `{}` is not expected on the HIP path (the hnd/ghnd configs use Adam, the ext '
-                     'config SGD)'.format(optim_type))
+    if optim_type.lower() == 'adagrad':
+        return FusedAdagrad(params, **optim_params_config)
+    if optim_type.lower() == 'rmsprop':
+        return FusedRMSprop(params, **optim_params_config)
+    raise ValueError('optim_type `{}` is not expected on the HIP path (SGD, Adam, Adagrad and RMSprop are; the hnd/ghnd '
+                     'configs use Adam, the ext config SGD)'.format(optim_type))
 
 
 def get_scheduler(optimizer, scheduler_type, scheduler_params_config):

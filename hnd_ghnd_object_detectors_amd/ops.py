@@ -1147,6 +1147,28 @@ def sgd_step_flat(param, grad, buf, lr, momentum, dampening, weight_decay, neste
     PARAM_EPOCH[0] += 1
 
 
+# include/hnd_optim.h: the state slots of each kind, in descriptor order (None: the kind has no such slot)
+OPTIM_STATE_SLOTS = {'adam': ('exp_avg', 'exp_avg_sq', 'max_exp_avg_sq'), 'adagrad': ('sum', None, None),
+                     'rmsprop': ('square_avg', 'momentum_buffer', 'grad_avg')}
+
+
+def optim_step_flat(kind, param, grad, states, numel=None, step=1, grad_scale=1.0, lr=0.0, weight_decay=0.0, eps=0.0,
+                    beta1=0.0, beta2=0.0, momentum=0.0, lr_decay=0.0, amsgrad=False, centered=False):
+    """one hnd_optim_step_flat launch.  kind: 'adam' | 'adagrad' | 'rmsprop'; states: up to three tensors (or None) in the
+    slot order of OPTIM_STATE_SLOTS[kind]; beta2 is RMSprop's alpha.  Arguments are validated by the library."""
+    states = tuple(states) + (None,) * (3 - len(states))
+    d = _lib.OptimDesc()
+    d.param, d.grad, d.state0, d.state1, d.state2 = ptr(param), ptr(grad), ptr(states[0]), ptr(states[1]), ptr(states[2])
+    d.numel, d.step = param.numel() if numel is None else int(numel), int(step)
+    d.grad_scale, d.lr, d.weight_decay, d.eps = float(grad_scale), float(lr), float(weight_decay), float(eps)
+    d.beta1, d.beta2, d.momentum, d.lr_decay = float(beta1), float(beta2), float(momentum), float(lr_decay)
+    d.kind, d.amsgrad, d.centered = _lib.OPTIM_KINDS[kind], int(bool(amsgrad)), int(bool(centered))
+    nbuf = 3 + 2 * sum(s is not None for s in states)                  # param r/w, grad r, every state r/w
+    _hbm('optim_' + kind, 4 * nbuf * d.numel, lambda: check(_L.hnd_optim_step_flat(C.byref(d), stream_ptr()),
+                                                           'hnd_optim_step_flat'))
+    PARAM_EPOCH[0] += 1
+
+
 def interp_out_size(size, scale):
     """F.interpolate(scale_factor=scale) output size: floor(size * scale) in double (torch semantics)."""
     return int(math.floor(float(size) * scale))

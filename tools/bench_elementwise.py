@@ -5,6 +5,8 @@ elementwise op moving the same bytes (what a plain streaming kernel reaches on t
 usage (GPU box):  python3 tools/bench_elementwise.py [--reps 30]
                   python3 tools/bench_elementwise.py --mimic-kinds [--rounds 9] [--out profiles/mimic_loss_kinds.txt]
                   (the loss launch per criterion kind beside MseLaunch, on the four maps of the default step)
+                  python3 tools/bench_elementwise.py --optim-kinds [--rounds 9] [--out FILE]
+                  (hnd_optim_step_flat per kind beside hnd_adam_step_flat, at the student's arena size and at 64 M elements)
 """
 import argparse
 import os
@@ -81,14 +83,73 @@ def mimic_kinds(a, out_path=None):
             f.write(text + '\n')
 
 
+def optim_kinds(a, out_path=None):
+    """hnd_optim_step_flat for every kind / flag combination beside hnd_adam_step_flat on the same buffers, at the flat
+    arena of the b3ch student (586 566 floats, include/hnd_hip.h) and at 64 M elements.  `rounds` repeats, the variants
+    interleaved inside each; a repeat is the mean of `reps` launches between two HIP events.  Bytes per element: the
+    parameter and every state are read and written, the gradient is read."""
+    from hnd_ghnd_object_detectors_amd import ops
+    dev = torch.device('cuda:0')
+    lines = []
+    for numel in (586566, 64 * 1024 * 1024):
+        p, g = torch.randn(numel, device=dev), torch.randn(numel, device=dev)
+        s = [torch.rand(numel, device=dev) for _ in range(3)]
+        variants = [('hnd_adam_step_flat', 28, lambda: ops.adam_step_flat(p, g, s[0], s[1], 1e-9, 0.9, 0.999, 1e-8, 7))]
+
+        def add(name, kind, states, **hyper):
+            nbytes = 4 * (3 + 2 * sum(t is not None for t in states))
+            variants.append((name, nbytes, lambda: ops.optim_step_flat(kind, p, g, states, step=7, lr=1e-9, eps=1e-8, **hyper)))
+        add('adam weight_decay', 'adam', s[:2], beta1=0.9, beta2=0.999, weight_decay=1e-4)
+        add('adam amsgrad', 'adam', s, beta1=0.9, beta2=0.999, amsgrad=True)
+        add('adam weight_decay amsgrad', 'adam', s, beta1=0.9, beta2=0.999, weight_decay=1e-4, amsgrad=True)
+        add('adagrad', 'adagrad', s[:1], lr_decay=0.1, weight_decay=1e-4)
+        add('rmsprop', 'rmsprop', s[:1], beta2=0.99)
+        add('rmsprop momentum', 'rmsprop', s[:2], beta2=0.99, momentum=0.9)
+        add('rmsprop centered', 'rmsprop', [s[0], None, s[2]], beta2=0.99, centered=True)
+        add('rmsprop centered momentum', 'rmsprop', s, beta2=0.99, momentum=0.9, centered=True)
+        for _, _, fn in variants:
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        for _ in range(a.rounds):
+            for i, (_, _, fn) in enumerate(variants):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for _ in range(a.reps):
+                    fn()
+                e1.record()
+                e1.synchronize()
+                times[i].append(e0.elapsed_time(e1) / a.reps * 1e3)
+        ops.sync_check()
+        med = [sorted(t)[len(t) // 2] for t in times]
+        lines.append('%d elements, %d rounds x %d launches, interleaved' % (numel, a.rounds, a.reps))
+        lines.append('%-28s %6s %10s %9s %9s %8s  %s' % ('launch', 'B/elem', 'median us', 'min us', 'max us', 'TB/s',
+                                                        'us per (B/elem), hnd_adam_step_flat = 1'))
+        for (name, nb, _), t, m in zip(variants, times, med):
+            lines.append('%-28s %6d %10.2f %9.2f %9.2f %8.3f  %.3f' % (name, nb, m, min(t), max(t), nb * numel / m / 1e6,
+                                                                     (m / nb) / (med[0] / 28)))
+        del p, g, s, variants
+    text = '\n'.join(lines)
+    print(text, flush=True)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, 'w') as f:
+            f.write(text + '\n')
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--batch', type=int, default=16)
     ap.add_argument('--mimic-kinds', action='store_true', help='only the loss launch, per criterion kind, beside MseLaunch')
-    ap.add_argument('--rounds', type=int, default=7, help='--mimic-kinds: interleaved repeats of every variant')
-    ap.add_argument('--out', help='--mimic-kinds: also write the table to this file')
+    ap.add_argument('--optim-kinds', action='store_true', help='only the optimizer launches of include/hnd_optim.h, per '
+                    'kind, beside hnd_adam_step_flat')
+    ap.add_argument('--rounds', type=int, default=7, help='--mimic-kinds / --optim-kinds: interleaved repeats of every variant')
+    ap.add_argument('--out', help='--mimic-kinds / --optim-kinds: also write the table to this file')
     a = ap.parse_args()
+    if a.optim_kinds:
+        return optim_kinds(a, a.out)
     if a.mimic_kinds:
         return mimic_kinds(a, a.out)
     from hnd_ghnd_object_detectors_amd import ops
