@@ -1,5 +1,6 @@
 """ctypes binding of libhnd_hip.so (C ABI declared in include/hnd_hip.h; the further optimizer kinds in
-include/hnd_optim.h, with a table and a version of their own).
+include/hnd_optim.h and the 1 ... 8-bit bottleneck codec in include/hnd_codec.h, each with a table and a version of its
+own).
 
 The library is the ONLY compute path of this package: if it is missing the import of any
 compute module fails loudly (no CPU / eager fallback exists on purpose).
@@ -193,6 +194,20 @@ _OPTIM_SIGNATURES = {
 
 OPTIM_SYMBOLS = tuple(sorted(_OPTIM_SIGNATURES))
 
+# ---- include/hnd_codec.h: the bottleneck codec at 1 ... 8 bits and its bit-packed payload; again a version and a table of
+# its own
+CODEC_ABI = 1
+
+_CODEC_SIGNATURES = {
+    'hnd_codec_abi': (C.c_int, []),
+    'hnd_codec_packed_bytes': (C.c_size_t, [C.c_int64, C.c_int]),
+    'hnd_quantize_bits': (C.c_int, [vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+    'hnd_quantize_pack_bits': (C.c_int, [vp] + [C.c_int] * 6 + [vp, vp, vp, vp]),
+    'hnd_unpack_dequantize_bits': (C.c_int, [vp, vp, vp] + [C.c_int] * 6 + [vp]),
+}
+
+CODEC_SYMBOLS = tuple(sorted(_CODEC_SIGNATURES))
+
 _lib = None
 
 
@@ -215,7 +230,8 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()):
+    for name, (res, args) in list(_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + \
+            list(_CODEC_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -226,6 +242,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so ABI %d != expected %d' % (lib.hnd_abi_version(), ABI_VERSION))
     if lib.hnd_optim_abi() != OPTIM_ABI:
         raise HndLibraryError('libhnd_hip.so optimizer ABI %d != expected %d' % (lib.hnd_optim_abi(), OPTIM_ABI))
+    if lib.hnd_codec_abi() != CODEC_ABI:
+        raise HndLibraryError('libhnd_hip.so codec ABI %d != expected %d' % (lib.hnd_codec_abi(), CODEC_ABI))
     _lib = lib
     return lib
 

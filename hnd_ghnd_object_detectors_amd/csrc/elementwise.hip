@@ -3,6 +3,7 @@
 // All are streaming passes: 16-byte accesses per lane, grid-stride over <= 2048*8 blocks,
 // per-wave shuffle reductions then per-block partials (no float atomics -> deterministic).
 #include "common.h"
+#include "hnd_codec.h"
 
 #include <hip/hip_fp16.h>
 #include <float.h>
@@ -1179,6 +1180,66 @@ __global__ void dequantize_kernel(const uint8_t* __restrict__ q, const float* __
     x[e] = ((int)(e % cs) < c) ? __fmul_rn(scale, __fsub_rn((float)q[e], zp)) : 0.f;      // scale * (q - zero_point)
 }
 
+// The bit-packed payload of include/hnd_codec.h: value i of the logical NCHW tensor sits in bits [i * bits, (i + 1) * bits)
+// of the byte stream, LSB first.  One thread owns a GROUP of 8 consecutive values = `bits` whole bytes starting at byte
+// group * bits, so no two threads share a byte and every store is a plain byte store.  The values of a group are gathered
+// from the NHWC buffer (a group may cross a row, a channel plane or an image) and quantised with quantize_kernel's fp32
+// sequence.  The last group holds numel % 8 values when that is not 0 and stores ceil(rem * bits / 8) bytes.
+__global__ void quantize_pack_kernel(const float* __restrict__ x, long long numel, int c, long long hw, int cs, int bits,
+                                     const float* __restrict__ qp, float qmax, uint8_t* __restrict__ payload) {
+#pragma clang fp contract(off)
+  const float scale = qp[2], zp = qp[3];
+  const long long groups = (numel + 7) >> 3;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups;
+       g += (long long)gridDim.x * blockDim.x) {
+    const long long i0 = g << 3;
+    const int count = numel - i0 < 8 ? (int)(numel - i0) : 8;
+    long long plane = i0 / hw, pix = i0 - plane * hw;               // plane = img * c + ch
+    long long img = plane / c;
+    int ch = (int)(plane - img * c);
+    unsigned long long word = 0;
+    for (int k = 0; k < count; ++k) {
+      float v = __fadd_rn(zp, __fdiv_rn(x[(img * hw + pix) * cs + ch], scale));     // zero_point + x / scale
+      v = v < 0.f ? 0.f : (v > qmax ? qmax : v);                   // clamp_(qmin, qmax)
+      v = rintf(v);                                                // round_(): half to even
+      word |= (unsigned long long)(unsigned)v << (k * bits);
+      if (++pix == hw) {
+        pix = 0;
+        if (++ch == c) { ch = 0; ++img; }
+      }
+    }
+    const int nbytes = (count * bits + 7) >> 3;                    // `bits` for a full group
+    uint8_t* dst = payload + g * bits;
+    for (int b = 0; b < nbytes; ++b) dst[b] = (uint8_t)(word >> (8 * b));
+  }
+}
+
+// One thread per float of the NHWC destination: real channels read their value's bits (at most two bytes: bits <= 8; the
+// second byte is touched only when the value reaches into it, so never past the payload's last byte), pad channels get 0.
+__global__ void unpack_dequantize_kernel(const uint8_t* __restrict__ payload, const float* __restrict__ qp,
+                                         float* __restrict__ x, long long npix, int c, long long hw, int cs, int bits) {
+#pragma clang fp contract(off)
+  const float scale = qp[2], zp = qp[3];
+  const long long total = npix * cs;
+  const unsigned mask = (1u << bits) - 1u;
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long p = e / cs;
+    const int ch = (int)(e - p * cs);
+    float v = 0.f;
+    if (ch < c) {
+      const long long img = p / hw, pix = p - img * hw;
+      const long long bit = ((img * c + ch) * hw + pix) * bits;
+      const long long byte = bit >> 3;
+      const int sh = (int)(bit & 7);
+      unsigned two = payload[byte];
+      if (sh + bits > 8) two |= (unsigned)payload[byte + 1] << 8;
+      v = __fmul_rn(scale, __fsub_rn((float)((two >> sh) & mask), zp));             // scale * (q - zero_point)
+    }
+    x[e] = v;
+  }
+}
+
 __global__ void roundtrip_f16_kernel(float* x, long long n) {
   for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
     x[e] = __half2float(__float2half(x[e]));
@@ -1660,6 +1721,63 @@ int hnd_dequantize_u8(const uint8_t* q, const float* qparams, float* x, int64_t 
   hipLaunchKernelGGL(dequantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, hnd::as_stream(stream), q,
                      qparams, x, (long long)npix, c, cs);
   return hnd::check_launch("hnd_dequantize_u8");
+}
+
+// ---- include/hnd_codec.h: the codec at 1 ... 8 bits and the bit-packed payload
+int hnd_codec_abi(void) { return HND_CODEC_ABI; }
+
+size_t hnd_codec_packed_bytes(int64_t numel, int bits) {
+  if (numel <= 0 || bits < 1 || bits > 8) return 0;
+  return (size_t)(numel >> 3) * bits + (size_t)(((numel & 7) * bits + 7) >> 3);      // ceil(numel * bits / 8), no overflow
+}
+
+// the two launches every quantising export starts with: per-block min / max of the real channels, then qparams
+static void launch_qparams(const float* x, long long npix, int c, int cs, float qmax, float* qparams, float* scratch,
+                           hipStream_t s) {
+  int nb = grid_for(npix * cs);
+  if (nb > kMinMaxBlocks) nb = kMinMaxBlocks;
+  hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(256), 0, s, x, npix, c, cs, scratch);
+  hipLaunchKernelGGL(qparams_kernel, dim3(1), dim3(64), 0, s, scratch, nb, qmax, qparams);
+}
+
+int hnd_quantize_bits(const float* x, int64_t npix, int c, int cs, int bits, uint8_t* q, float* qparams, float* scratch,
+                      void* stream) {
+  HND_REQUIRE(x && q && qparams && scratch, "hnd_quantize_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c, "hnd_quantize_bits: bad geometry (npix > 0, c > 0, cs >= c)");
+  hipStream_t s = hnd::as_stream(stream);
+  const float qmax = (float)((1 << bits) - 1);
+  launch_qparams(x, (long long)npix, c, cs, qmax, qparams, scratch, s);
+  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, s, x, (long long)npix, c, cs,
+                     qparams, qmax, q);
+  return hnd::check_launch("hnd_quantize_bits");
+}
+
+int hnd_quantize_pack_bits(const float* x, int n, int h, int w, int c, int cs, int bits, uint8_t* payload, float* qparams,
+                           float* scratch, void* stream) {
+  HND_REQUIRE(x && payload && qparams && scratch, "hnd_quantize_pack_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_pack_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c,
+              "hnd_quantize_pack_bits: bad geometry (n, h, w, c > 0, cs >= c)");
+  hipStream_t s = hnd::as_stream(stream);
+  const float qmax = (float)((1 << bits) - 1);
+  const long long hw = (long long)h * w, npix = hw * n, numel = npix * c;
+  launch_qparams(x, npix, c, cs, qmax, qparams, scratch, s);
+  hipLaunchKernelGGL(quantize_pack_kernel, dim3(grid_for((numel + 7) / 8)), dim3(256), 0, s, x, numel, c, hw, cs, bits,
+                     qparams, qmax, payload);
+  return hnd::check_launch("hnd_quantize_pack_bits");
+}
+
+int hnd_unpack_dequantize_bits(const uint8_t* payload, const float* qparams, float* x, int n, int h, int w, int c, int cs,
+                               int bits, void* stream) {
+  HND_REQUIRE(payload && qparams && x, "hnd_unpack_dequantize_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_unpack_dequantize_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c,
+              "hnd_unpack_dequantize_bits: bad geometry (n, h, w, c > 0, cs >= c)");
+  const long long hw = (long long)h * w, npix = hw * n;
+  hipLaunchKernelGGL(unpack_dequantize_kernel, dim3(grid_for(npix * cs)), dim3(256), 0, hnd::as_stream(stream), payload,
+                     qparams, x, npix, c, hw, cs, bits);
+  return hnd::check_launch("hnd_unpack_dequantize_bits");
 }
 
 int hnd_roundtrip_f16(float* x, int64_t numel, void* stream) {

@@ -87,8 +87,11 @@ class _ShapeOnly(object):
         self.shape = tuple(shape)
 
 
-def split_rcnn_model(model, quantization):
-    """reference :215-221; ``quantization``: None, 8 or 16 (bits of the bottleneck codec)."""
-    encoder_transformer = None if quantization is None else Compose([Quantizer(num_bits=quantization)])
+def split_rcnn_model(model, quantization, packed=False):
+    """reference :215-221; ``quantization``: None, 1 ... 8 or 16 (bits of the bottleneck codec).  ``packed`` (1 ... 8 bits):
+    the head emits the bit-packed link payload (structure.transformer.PackedBottleneck) and the tail unpacks it."""
+    if quantization is None and packed:
+        raise ValueError('split_rcnn_model(packed=True) needs a quantization width (1 ... 8)')
+    encoder_transformer = None if quantization is None else Compose([Quantizer(num_bits=quantization, packed=packed)])
     decoder_transformer = None if quantization is None else Compose([Dequantizer(num_bits=quantization)])
     return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)

@@ -733,6 +733,39 @@ def minmax_scratch_elems():
     return _L.hnd_minmax_scratch_elems()
 
 
+# include/hnd_codec.h: the codec at 1 ... 8 bits.  x is the NHWC fp32 buffer [N, H, W, cs] with c real channels.
+def codec_packed_bytes(numel, bits):
+    """bytes of the bit-packed payload of `numel` values at `bits` bits each: ceil(numel * bits / 8); 0 for bad arguments"""
+    return int(_L.hnd_codec_packed_bytes(int(numel), int(bits)))
+
+
+def quantize_bits(x, c, bits, q, qparams, scratch):
+    """quantize_u8 with qmax = 2^bits - 1: one value per byte into q (uint8, x's shape), pad channels 0"""
+    cs = x.shape[-1]
+    assert q.numel() == x.numel() and q.dtype == torch.uint8
+    check(_L.hnd_quantize_bits(ptr(x), x.numel() // cs, c, cs, int(bits), ptr(q), ptr(qparams), ptr(scratch),
+                               stream_ptr()), 'hnd_quantize_bits')
+
+
+def quantize_pack_bits(x, c, bits, payload, qparams, scratch):
+    """quantise the c real channels of x and pack them, in logical NCHW order, LSB first, into the 1-D uint8 `payload` of
+    exactly codec_packed_bytes(N * c * H * W, bits) bytes (format: include/hnd_codec.h)"""
+    n, h, w, cs = x.shape
+    assert payload.dtype == torch.uint8 and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0, \
+        (tuple(payload.shape), (n, c, h, w), bits)
+    check(_L.hnd_quantize_pack_bits(ptr(x), n, h, w, c, cs, int(bits), ptr(payload), ptr(qparams), ptr(scratch),
+                                    stream_ptr()), 'hnd_quantize_pack_bits')
+
+
+def unpack_dequantize_bits(payload, qparams, x, c, bits):
+    """the inverse: scale * (q - zero_point) into the c real channels of x [N, H, W, cs], 0 into its pad channels"""
+    n, h, w, cs = x.shape
+    assert payload.dtype == torch.uint8 and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0, \
+        (tuple(payload.shape), (n, c, h, w), bits)
+    check(_L.hnd_unpack_dequantize_bits(ptr(payload), ptr(qparams), ptr(x), n, h, w, c, cs, int(bits), stream_ptr()),
+          'hnd_unpack_dequantize_bits')
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

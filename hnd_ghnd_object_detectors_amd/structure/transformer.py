@@ -2,8 +2,9 @@
 
 The reference applies them ONLY at evaluation time with ``-transform_bottleneck`` (src/models/mimic/base.py:54-57;
 mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantizer`` run as fused HIP kernels
-(global min/max -> affine uint8 quantise; dequantise) on the NHWC bottleneck buffer; the 16-bit variants are a
-half round trip.  ``JpegCompressor`` / ``JpegDecompressor`` (:94-128: the uint8 bottleneck image through a JPEG file)
+(global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
+payload, include/hnd_codec.h; dequantise) on the NHWC bottleneck buffer; the 16-bit variants are a half round trip.
+``JpegCompressor`` / ``JpegDecompressor`` (:94-128: the uint8 bottleneck image through a JPEG file)
 and ``DataLogger`` (:58-91: pickled sizes of the bottleneck for the reference's cost analysis) are host-side file /
 bookkeeping utilities: the quantisation they contain runs on the same HIP kernel, the rest is PIL / pickle as in the
 reference.
@@ -160,7 +161,8 @@ class DataLogger(object):
             sizes = (file_util.get_binary_object_size(z), None, None)
         else:
             plain = z.detach().cpu().contiguous()               # logical NCHW values, as the reference pickles them
-            qz, _ = Quantizer(self.num_bits4quant)(z, None) if self.num_bits4quant == 8 else (plain.half(), None)
+            # 1 ... 8 bits: the real quantiser, whose uint8 tensor the reference pickles at any of these widths
+            qz, _ = Quantizer(self.num_bits4quant)(z, None) if self.num_bits4quant in range(1, 9) else (plain.half(), None)
             if isinstance(qz, QuantizedTensor):                  # what crosses the link: uint8 tensor + scale + zero point
                 qz = _HostQuantized(qz.tensor.cpu().contiguous(), float(qz.scale), int(qz.zero_point))
             sizes = (file_util.get_binary_object_size(plain), file_util.get_binary_object_size(plain.short()),
@@ -232,11 +234,40 @@ class QuantizedTensor(object):
         self.qparams, self.origin, self.channels = qparams, origin, channels
 
 
+class PackedBottleneck(object):
+    """The quantised bottleneck as it crosses the link (``Quantizer(num_bits, packed=True)``): ``payload`` is a 1-D uint8
+    device tensor of exactly ceil(numel * num_bits / 8) bytes holding the values of the logical NCHW tensor ``shape``
+    back to back, ``num_bits`` each, least significant bit first (format: include/hnd_codec.h); ``scale`` /
+    ``zero_point`` are 0-dim device views of ``qparams`` as in QuantizedTensor.  An extension: the reference ships the
+    one-value-per-byte tensor whatever the width."""
+
+    def __init__(self, payload, shape, num_bits, qparams, origin=None):
+        self.payload, self.shape, self.num_bits = payload, tuple(int(s) for s in shape), num_bits
+        self.qparams, self.scale, self.zero_point, self.origin = qparams, qparams[2], qparams[3], origin
+
+    @property
+    def nbytes(self):
+        return self.payload.numel()
+
+
+SUPPORTED_BITS = tuple(range(1, 9)) + (16,)
+
+
+def _check_bits(who, num_bits, packed=False):
+    if isinstance(num_bits, bool) or num_bits not in SUPPORTED_BITS or (packed and num_bits == 16):
+        raise NotImplementedError('%s(num_bits=%r%s): the HIP bottleneck codec implements num_bits in %s%s' % (
+            who, num_bits, ', packed=True' if packed else '', list(SUPPORTED_BITS),
+            ' and packs 1 ... 8 bits only (16 is a half round trip, nothing to pack)' if packed else ''))
+
+
 class Quantizer(object):
-    def __init__(self, num_bits=8):
-        if num_bits not in (8, 16):
-            raise NotImplementedError('HIP bottleneck codec implements 8- and 16-bit quantisation')
-        self.num_bits = num_bits
+    """reference :131-140 at any width the reference's uint8 tensor can hold: 1 ... 8 bits (qmax = 2^num_bits - 1), or
+    16 (half round trip).  ``packed=True`` returns the bit-packed link payload (PackedBottleneck) instead of the
+    one-value-per-byte QuantizedTensor."""
+
+    def __init__(self, num_bits=8, packed=False):
+        _check_bits('Quantizer', num_bits, packed)
+        self.num_bits, self.packed = num_bits, bool(packed)
         self._bufs = {}
 
     def __call__(self, z, target):
@@ -245,22 +276,43 @@ class Quantizer(object):
         if self.num_bits == 16:             # z.half(): stored back as the fp32 value of the half
             ops.roundtrip_f16(buf)
             return z, target
-        key = (tuple(buf.shape), buf.device)
+        key = (tuple(buf.shape), c, buf.device)
         if key not in self._bufs:
-            self._bufs[key] = (torch.empty(buf.shape, dtype=torch.uint8, device=buf.device),
+            n, h, w, _ = buf.shape
+            qshape = (ops.codec_packed_bytes(n * c * h * w, self.num_bits),) if self.packed else buf.shape
+            self._bufs[key] = (torch.empty(qshape, dtype=torch.uint8, device=buf.device),
                                torch.empty(4, dtype=torch.float32, device=buf.device),
                                torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         q, qparams, scratch = self._bufs[key]
-        ops.quantize_u8(buf, c, q, qparams, scratch)
+        if self.packed:
+            ops.quantize_pack_bits(buf, c, self.num_bits, q, qparams, scratch)
+            return PackedBottleneck(q, z.shape, self.num_bits, qparams, origin=buf), target
+        if self.num_bits == 8:
+            ops.quantize_u8(buf, c, q, qparams, scratch)
+        else:
+            ops.quantize_bits(buf, c, self.num_bits, q, qparams, scratch)
         qt = q[..., :c].permute(0, 3, 1, 2)
         return QuantizedTensor(attach(qt, q), qparams[2], qparams[3], qparams, origin=buf, channels=c), target
 
 
 class Dequantizer(object):
+    """reference :143-153.  A QuantizedTensor of any width goes through the one dequantise kernel (the width lives in its
+    scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``."""
+
     def __init__(self, num_bits=8):
+        _check_bits('Dequantizer', num_bits)
         self.num_bits = num_bits
 
     def __call__(self, qz, target):
+        if isinstance(qz, PackedBottleneck):
+            if qz.num_bits != self.num_bits:
+                raise ValueError('Dequantizer(num_bits=%d) was handed a payload packed at %d bits'
+                                 % (self.num_bits, qz.num_bits))
+            n, c, h, w = qz.shape
+            out = qz.origin if qz.origin is not None else \
+                torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
+            ops.unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
+            return attach(out[..., :c].permute(0, 3, 1, 2), out), target
         if self.num_bits == 16 or not isinstance(qz, QuantizedTensor):
             return qz, target
         q = qz.tensor._hnd
