@@ -1,6 +1,6 @@
 """ctypes binding of libhnd_hip.so (C ABI declared in include/hnd_hip.h; the further optimizer kinds in
-include/hnd_optim.h and the 1 ... 8-bit bottleneck codec in include/hnd_codec.h, each with a table and a version of its
-own).
+include/hnd_optim.h, the 1 ... 8-bit bottleneck codec in include/hnd_codec.h and the fake-quantised bottleneck of the
+training step in include/hnd_qat.h, each with a table and a version of its own).
 
 The library is the ONLY compute path of this package: if it is missing the import of any
 compute module fails loudly (no CPU / eager fallback exists on purpose).
@@ -208,6 +208,17 @@ _CODEC_SIGNATURES = {
 
 CODEC_SYMBOLS = tuple(sorted(_CODEC_SIGNATURES))
 
+# ---- include/hnd_qat.h: the fake-quantised bottleneck of the training step; a version and a table of its own as well
+QAT_ABI = 1
+
+_QAT_SIGNATURES = {
+    'hnd_qat_abi': (C.c_int, []),
+    'hnd_fake_quantize_tiles': (C.c_int, [C.c_int64]),
+    'hnd_fake_quantize_bits': (C.c_int, [vp, vp, C.c_int64, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]),
+}
+
+QAT_SYMBOLS = tuple(sorted(_QAT_SIGNATURES))
+
 _lib = None
 
 
@@ -231,7 +242,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(_SIGNATURES.items()) + list(_OPTIM_SIGNATURES.items()) + \
-            list(_CODEC_SIGNATURES.items()):
+            list(_CODEC_SIGNATURES.items()) + list(_QAT_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:
@@ -244,6 +255,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so optimizer ABI %d != expected %d' % (lib.hnd_optim_abi(), OPTIM_ABI))
     if lib.hnd_codec_abi() != CODEC_ABI:
         raise HndLibraryError('libhnd_hip.so codec ABI %d != expected %d' % (lib.hnd_codec_abi(), CODEC_ABI))
+    if lib.hnd_qat_abi() != QAT_ABI:
+        raise HndLibraryError('libhnd_hip.so fake-quantisation ABI %d != expected %d' % (lib.hnd_qat_abi(), QAT_ABI))
     _lib = lib
     return lib
 

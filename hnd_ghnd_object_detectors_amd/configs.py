@@ -15,8 +15,42 @@ def _term(layer):
             'factor': 1.0}
 
 
+ENCODER_PATH = 'backbone.body.layer1.encoder'
+
+
+def fake_quantize_bits_of(config):
+    """the width of the optional section ``train.fake_quantize: {num_bits: b}`` (quantisation-aware distillation, an
+    extension: the reference has no such key), or None when the section is absent.  Refused by name here, at config time:
+    a width outside 1 ... 8, and a criterion term whose student module is the bottleneck tensor's (layer1.encoder)."""
+    train = config.get('train') or {}
+    section = train.get('fake_quantize')
+    if section is None:
+        return None
+    if not isinstance(section, dict) or set(section) != {'num_bits'}:
+        raise ValueError('train.fake_quantize must be {num_bits: b}, got %r' % (section,))
+    bits = section['num_bits']
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
+        raise ValueError('train.fake_quantize.num_bits=%r is outside 1 ... 8, the widths the fake-quantised bottleneck '
+                         'implements' % (bits,))
+    terms = ((train.get('criterion') or {}).get('terms') or {})
+    for name, term in terms.items():
+        if list(term.get('ts_modules', ()))[1:2] == [ENCODER_PATH]:
+            raise NotImplementedError('train.fake_quantize together with the loss term `%s` on %s is not built: the '
+                                      'bottleneck tensor is quantised in place, so the unquantised tensor the reference\'s '
+                                      'hook would see does not exist' % (name, ENCODER_PATH))
+    return bits
+
+
 def make_config(model='faster_rcnn', method='ghnd', bch=3, batch_size=4, pretrained=True, min_size=None,
-                max_size=None, ckpt_root='./resource/ckpt'):
+                max_size=None, ckpt_root='./resource/ckpt', fake_quantize_bits=None):
+    config = _make_config(model, method, bch, batch_size, pretrained, min_size, max_size, ckpt_root)
+    if fake_quantize_bits is not None:
+        config['train']['fake_quantize'] = {'num_bits': fake_quantize_bits}
+        fake_quantize_bits_of(config)
+    return config
+
+
+def _make_config(model, method, bch, batch_size, pretrained, min_size, max_size, ckpt_root):
     assert model in MODELS and method in ('hnd', 'ghnd')
     keypoint = model == 'keypoint_rcnn'
     dataset = 'coco2017'

@@ -4,9 +4,11 @@
 // per-wave shuffle reductions then per-block partials (no float atomics -> deterministic).
 #include "common.h"
 #include "hnd_codec.h"
+#include "hnd_qat.h"
 
 #include <hip/hip_fp16.h>
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 
 namespace {
@@ -1240,6 +1242,73 @@ __global__ void unpack_dequantize_kernel(const uint8_t* __restrict__ payload, co
   }
 }
 
+// include/hnd_qat.h: quantise and dequantise in one pass (quantize_kernel's then dequantize_kernel's fp32 sequence, the code
+// kept in a register instead of a byte: (float)(uint8_t)q == q for the integers 0 ... 255), in place or not, with the
+// BatchNorm partial sums of what was stored.  One WAVE per tile of kFqRows pixels; the wave's lanes are laid out as
+// (row, channel group of 4) with the group fastest, so a wave's 16-byte loads cover consecutive bytes and a lane keeps its
+// group for the whole tile (64 / groups rows per pass; a pixel wider than 64 groups is walked 64 groups at a time).  The
+// per-lane sums meet in LDS and are added in row-slot order: a fixed order, no atomics.  x and y may be the same buffer
+// (every float is read and written by one lane), so neither is __restrict__.
+constexpr int kFqRows = HND_FAKE_QUANT_TILE_ROWS;
+constexpr int kFqWaves = 4;
+
+__global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const float* x, float* y, long long npix, int c,
+                                                                      int cs, const float* __restrict__ qp, float qmax,
+                                                                      float* __restrict__ stats, int ntiles) {
+#pragma clang fp contract(off)
+  __shared__ float red[kFqWaves][64][8];
+  const float scale = qp[2], zp = qp[3];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int groups = cs >> 2;
+  for (int t0 = blockIdx.x * kFqWaves; t0 < ntiles; t0 += gridDim.x * kFqWaves) {      // (uniform over the block)
+    const int tile = t0 + wave;
+    const long long row0 = (long long)tile * kFqRows;
+    const int rows = tile < ntiles ? (npix - row0 < kFqRows ? (int)(npix - row0) : kFqRows) : 0;
+    for (int gb = 0; gb < groups; gb += 64) {
+      const int gc = groups - gb < 64 ? groups - gb : 64;         // groups in this pass
+      const int slots = 64 / gc;                                  // rows per pass
+      const int gl = lane % gc, slot = lane / gc;
+      const int ch0 = (gb + gl) * 4;
+      float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
+      if (slot < slots) {
+        for (int r = slot; r < rows; r += slots) {
+          const long long e = (row0 + r) * cs + ch0;
+          const f32x4 v = *(const f32x4*)(x + e);
+          f32x4 o;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            float q = 0.f;
+            if (ch0 + k < c) {
+              q = __fadd_rn(zp, __fdiv_rn(v[k], scale));            // zero_point + x / scale
+              q = q < 0.f ? 0.f : (q > qmax ? qmax : q);           // clamp_(qmin, qmax)
+              q = rintf(q);                                        // round_(): half to even
+              q = __fmul_rn(scale, __fsub_rn(q, zp));              // scale * (q - zero_point)
+            }
+            o[k] = q;
+            s[k] += q;
+            ss[k] += q * q;
+          }
+          *(f32x4*)(y + e) = o;
+        }
+      }
+      if (stats != nullptr) {                                     // (uniform over the block)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { red[wave][lane][k] = s[k]; red[wave][lane][4 + k] = ss[k]; }
+        __syncthreads();
+        if (rows > 0) {
+          for (int i = lane; i < gc * 8; i += 64) {
+            const int g = i >> 3, k = i & 7;
+            float acc = 0.f;
+            for (int sl = 0; sl < slots; ++sl) acc += red[wave][sl * gc + g][k];
+            stats[((size_t)tile * 2 + (k >> 2)) * cs + (gb + g) * 4 + (k & 3)] = acc;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+}
+
 __global__ void roundtrip_f16_kernel(float* x, long long n) {
   for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
     x[e] = __half2float(__float2half(x[e]));
@@ -1778,6 +1847,34 @@ int hnd_unpack_dequantize_bits(const uint8_t* payload, const float* qparams, flo
   hipLaunchKernelGGL(unpack_dequantize_kernel, dim3(grid_for(npix * cs)), dim3(256), 0, hnd::as_stream(stream), payload,
                      qparams, x, npix, c, hw, cs, bits);
   return hnd::check_launch("hnd_unpack_dequantize_bits");
+}
+
+// ---- include/hnd_qat.h: the fake-quantised bottleneck of the training step
+int hnd_qat_abi(void) { return HND_QAT_ABI; }
+
+int hnd_fake_quantize_tiles(int64_t npix) {
+  if (npix <= 0) return 0;
+  const int64_t t = (npix + kFqRows - 1) / kFqRows;
+  return t > INT_MAX ? 0 : (int)t;
+}
+
+int hnd_fake_quantize_bits(const float* x, float* y, int64_t npix, int c, int cs, int bits, float* qparams, float* scratch,
+                           float* stats, void* stream) {
+  HND_REQUIRE(x && y && qparams && scratch, "hnd_fake_quantize_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_fake_quantize_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_fake_quantize_bits: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
+  const int ntiles = hnd_fake_quantize_tiles(npix);
+  HND_REQUIRE(ntiles > 0, "hnd_fake_quantize_bits: npix too large (the tile count must fit an int)");
+  HND_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "hnd_fake_quantize_bits: x and y must be 16-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  const float qmax = (float)((1 << bits) - 1);
+  launch_qparams(x, (long long)npix, c, cs, qmax, qparams, scratch, s);
+  int nb = (ntiles + kFqWaves - 1) / kFqWaves;
+  if (nb > kMaxBlocks) nb = kMaxBlocks;
+  hipLaunchKernelGGL(fake_quantize_kernel, dim3(nb), dim3(64 * kFqWaves), 0, s, x, y, (long long)npix, c, cs, qparams,
+                     qmax, stats, ntiles);
+  return hnd::check_launch("hnd_fake_quantize_bits");
 }
 
 int hnd_roundtrip_f16(float* x, int64_t numel, void* stream) {

@@ -133,6 +133,10 @@ class DistillationBox(nn.Module):
         return student_out
 
     def forward(self, images, targets):
+        student = unwrap(self.student_model)
+        layer1 = getattr(getattr(getattr(student, 'backbone', None), 'body', None), 'layer1', None)
+        if student.training and hasattr(layer1, 'fake_quant_bits_checked'):
+            layer1.fake_quant_bits_checked()        # quantisation-aware distillation: its refusals, before any launch
         extra = {}
         if self.require_adjustment:
             sizes = unwrap(self.teacher_model).transform.min_size

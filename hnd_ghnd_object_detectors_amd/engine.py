@@ -681,7 +681,19 @@ class HeadEngine(object):
     def bwd_out_bits(self):
         return getattr(self, 'out_bits', None)
 
-    def forward(self, x, training, codec=None):
+    def forward(self, x, training, codec=None, fake_quant_bits=None):
+        """fake_quant_bits (1 ... 8, training only; include/hnd_qat.h): the bottleneck tensor z = y[encoder_len - 1] is
+        quantised and dequantised IN PLACE between its conv and its BatchNorm (decoder.0), whose batch statistics then come
+        from the launch that stored the quantised values.  The backward plan is NOT changed, on purpose: the estimator is
+        straight-through (d z' / d z = 1), so dy of the encoder's last conv is what bn_bwd_apply leaves in g[zi] -- and
+        everything that reads y[zi] in the backward (bn_bwd_reduce / bn_bwd_apply, the weight gradient of the decoder's
+        first conv) must read the quantised values, which is what the buffer now holds.  No clamping mask is needed:
+        min / max come from the tensor itself, so zero_point + z / scale never leaves [0, qmax] by more than rounding."""
+        if fake_quant_bits is not None:
+            if isinstance(fake_quant_bits, bool) or not isinstance(fake_quant_bits, int) or not 1 <= fake_quant_bits <= 8:
+                raise ValueError('HeadEngine.forward: fake_quant_bits=%r is outside 1 ... 8' % (fake_quant_bits,))
+            if not training:
+                fake_quant_bits = None      # (the eval path is the codec's)
         if self.bufs is None:
             self.bufs = Buffers(x.device)
         ops.pack_batch_begin()              # the ~28 operand re-packs of a training step go out as one launch
@@ -695,12 +707,14 @@ class HeadEngine(object):
         ptrs = tuple(t.data_ptr() for hc in self.layers
                      for t in (hc.bn.weight, hc.bn.bias, hc.bn.running_mean, hc.bn.running_var))
         self._out_buf = self.out_provider(self.out_shape(x)) if self.out_provider is not None else None
-        key = (x.data_ptr(), tuple(x.shape), training, ptrs, None if self._out_buf is None else self._out_buf.data_ptr())
+        key = (x.data_ptr(), tuple(x.shape), training, ptrs, None if self._out_buf is None else self._out_buf.data_ptr(),
+               fake_quant_bits)
         if key != self.plan_key:
-            self._build_forward(x, training)
+            self._build_forward(x, training, fake_quant_bits)
             self.plan_key = key
             self.bwd_key = None
         b = self.bufs
+        zi = self.encoder_len - 1
         for i, hc in enumerate(self.layers):
             if not training:
                 # eval-mode BN: fold running statistics (eps 1e-5) into the next prologue
@@ -723,6 +737,11 @@ class HeadEngine(object):
             if training:
                 bn = hc.bn
                 m = self.count[i]
+                if self.fq is not None and i == zi:
+                    # z -> dequantise(quantise(z)) in place; self.stats[zi] / self.ntiles[zi] are the launch's own (the conv
+                    # epilogue's sums, of the unquantised values, stay in their buffer unread)
+                    qparams, scratch = self.fq
+                    ops.fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch, stats=self.stats[i])
                 ops.bn_finalize(self.stats[i], self.ntiles[i], hc.cout, hc.cs_out, m, bn.weight.detach(),
                                 bn.bias.detach(), bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 BN_MOMENTUM, BN_EPS, self.scale[i], self.shift[i], self.mean[i], self.rstd[i])
@@ -730,7 +749,7 @@ class HeadEngine(object):
                         mask_out=self.out_bits)
         return self.out
 
-    def _build_forward(self, x, training):
+    def _build_forward(self, x, training, fake_quant_bits=None):
         n, h, w, c = x.shape
         assert c == self.layers[0].cs_in
         b = self.bufs
@@ -774,6 +793,14 @@ class HeadEngine(object):
             self.count.append(m)
             cur, cur_scale, cur_shift, cur_relu = y, sc, sh, hc.relu
             h, w = oh, ow
+        self.fq = None
+        if training and fake_quant_bits is not None:
+            # the fake-quantising launch of forward(): qparams, min/max scratch, and BatchNorm partial sums in a buffer of
+            # its own (its tile count, not the conv epilogue's), which bn_finalize of the bottleneck's BatchNorm then reads
+            zi = self.encoder_len - 1
+            self.fq = (b.get('fq_qparams', (4,)), b.get('fq_scratch', (ops.minmax_scratch_elems(),)))
+            self.ntiles[zi] = ops.fake_quantize_tiles(self.count[zi])
+            self.stats[zi] = b.get('fq_stats', (self.ntiles[zi], 2, self.layers[zi].cs_out))
         self.out = b.get('out', (n, h, w, self.layers[-1].cs_out)) if self._out_buf is None else self._out_buf
         assert tuple(self.out.shape) == (n, h, w, self.layers[-1].cs_out)
         # ReLU mask of the layer output as nibbles, for the data gradient that enters this layer (MASK_BITS)

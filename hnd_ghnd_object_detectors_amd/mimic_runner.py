@@ -22,6 +22,7 @@ import time
 import torch
 from torch import distributed as dist
 
+from . import configs
 from .distillation.tool import DistillationBox
 from .models import get_model, load_ckpt, save_ckpt
 from .myutils.common import file_util, yaml_util
@@ -168,6 +169,10 @@ def distill(teacher_model, student_model, train_loader, val_loader, device, dist
         best_val_map = float(best_val_map or 0.0)
         best_loss = torch.load(ckpt_file_path, map_location='cpu', weights_only=False).get('best_loss')
     use_bottleneck_transformer = args.transform_bottleneck
+    # quantisation-aware distillation (an extension): train.fake_quantize.num_bits, absent = off; refused at config time
+    # for a bad width or a term on the bottleneck tensor.  Only train mode reads it: validation and the final evaluation
+    # run the real codec (or none), as -transform_bottleneck decides
+    student.backbone.body.layer1.train_fake_quant_bits = configs.fake_quantize_bits_of(config)
     started = time.time()
     for epoch in range(args.num_epochs or train_config['num_epochs']):
         if hasattr(train_loader, 'set_epoch'):
@@ -217,6 +222,7 @@ def main(args):
     config = yaml_util.load_yaml_file(args.config)
     if args.json is not None:
         main_util.overwrite_config(config, args.json)
+    configs.fake_quantize_bits_of(config)       # (a bad train.fake_quantize section is refused before anything is built)
     distributed, _ = main_util.init_distributed_mode(args.world_size, args.dist_url)
     main_util.limit_host_threads(int(os.environ.get('LOCAL_WORLD_SIZE') or 1))
     if not torch.cuda.is_available():

@@ -43,6 +43,10 @@ class BottleneckBase4Ext(nn.Module):
         self.encoder, self.decoder = encoder, decoder
         self.bottleneck_transformer = bottleneck_transformer
         self.use_bottleneck_transformer = False
+        # quantisation-aware distillation (an extension; yaml train.fake_quantize.num_bits, set by mimic_runner.distill):
+        # 1 ... 8 = in TRAIN mode the bottleneck tensor is quantised and dequantised at that width between encoder and
+        # decoder, straight-through in the backward (HeadEngine.forward); None = off, the reference's training
+        self.train_fake_quant_bits = None
         self.uses_ext_encoder = isinstance(encoder, ExtEncoder) and encoder.ext_classifier is not None
         from ...structure.transformer import DataLogger
         self.data_logging = isinstance(bottleneck_transformer, DataLogger)       # reference :34
@@ -57,6 +61,26 @@ class BottleneckBase4Ext(nn.Module):
             self._engine = E.HeadEngine(self.head_layers())
         return self._engine
 
+    def fake_quant_bits_checked(self):
+        """train_fake_quant_bits, or the refusals that go with it (by name, before any launch of this layer): a width
+        outside 1 ... 8; a forward hook on ``layer1.encoder`` (a loss term on the bottleneck tensor -- the reference's hook
+        would see the unquantised z, which no longer exists once the buffer is quantised in place); the shared trunk
+        (HND_MERGE_TRUNK=1), a combination no test runs."""
+        bits = self.train_fake_quant_bits
+        if bits is None:
+            return None
+        from ...structure.transformer import check_fake_quant_bits
+        check_fake_quant_bits('train_fake_quant_bits (train.fake_quantize.num_bits)', bits)
+        if self.encoder._forward_hooks:
+            raise NotImplementedError(
+                'fake quantisation (train.fake_quantize) together with a hook / loss term on backbone.body.layer1.encoder '
+                'is not built: the bottleneck tensor is quantised in place, so the unquantised tensor the reference\'s hook '
+                'would see does not exist')
+        if E.MERGE_TRUNK:
+            raise NotImplementedError('fake quantisation (train.fake_quantize) with the shared trunk on '
+                                      '(HND_MERGE_TRUNK=1) is not built')
+        return bits
+
     def forward(self, x):
         ext_z = None
         if self.uses_ext_encoder:                       # reference :38-48 via ExtEncoder.forward_with_ext
@@ -66,9 +90,11 @@ class BottleneckBase4Ext(nn.Module):
                     self.bottleneck_transformer(None, target=None)
                 return None, ext_z
         use_codec = self.use_bottleneck_transformer and not self.training and self.bottleneck_transformer is not None
+        fq_bits = self.fake_quant_bits_checked() if self.training else None
         eng = self.head_engine()
         out = eng.forward(to_nhwc(x), self.training,
-                          codec=self.bottleneck_transformer if use_codec else None)   # base.py:54-57
+                          codec=self.bottleneck_transformer if use_codec else None,   # base.py:54-57
+                          fake_quant_bits=fq_bits)
         body = self.__dict__.get('_body')
         z = None
         if self.encoder._forward_hooks or self.decoder._forward_hooks:

@@ -766,6 +766,33 @@ def unpack_dequantize_bits(payload, qparams, x, c, bits):
           'hnd_unpack_dequantize_bits')
 
 
+# include/hnd_qat.h: the fake-quantised bottleneck of the training step
+def fake_quantize_tiles(npix):
+    """rows of the `stats` buffer of fake_quantize_bits for npix pixels (128 pixels per row); 0 for npix <= 0"""
+    return int(_L.hnd_fake_quantize_tiles(int(npix)))
+
+
+def fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None):
+    """quantise and dequantise the c real channels of x [N, H, W, cs] at `bits` bits in one pass -- the bits of
+    dequantize_u8(quantize_bits(x)) -- into `out` (default: in place), 0 into the pad channels; `stats`
+    [fake_quantize_tiles(npix), 2, cs] receives the per-tile (sum, sum of squares) of what was stored, for bn_finalize.
+    Returns the destination."""
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
+        raise ValueError('fake_quantize_bits: bits=%r outside 1 ... 8' % (bits,))
+    cs = x.shape[-1]
+    npix = x.numel() // cs
+    out = x if out is None else out
+    assert x.is_contiguous() and out.is_contiguous() and x.dtype == out.dtype == torch.float32
+    assert tuple(out.shape) == tuple(x.shape), (tuple(out.shape), tuple(x.shape))
+    assert qparams.numel() >= 4 and scratch.numel() >= minmax_scratch_elems()
+    if stats is not None:
+        assert stats.is_contiguous() and stats.dtype == torch.float32 and \
+            stats.numel() == fake_quantize_tiles(npix) * 2 * cs, (tuple(stats.shape), npix, cs)
+    check(_L.hnd_fake_quantize_bits(ptr(x), ptr(out), npix, c, cs, bits, ptr(qparams), ptr(scratch), ptr(stats),
+                                    stream_ptr()), 'hnd_fake_quantize_bits')
+    return out
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

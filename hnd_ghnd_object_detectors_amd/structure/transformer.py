@@ -4,6 +4,8 @@ The reference applies them ONLY at evaluation time with ``-transform_bottleneck`
 mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantizer`` run as fused HIP kernels
 (global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
 payload, include/hnd_codec.h; dequantise) on the NHWC bottleneck buffer; the 16-bit variants are a half round trip.
+``FakeQuantizer`` (an extension) is the pair as one call (include/hnd_qat.h) -- the launch the TRAINING step runs on the
+bottleneck tensor when ``train.fake_quantize`` is set (engine.HeadEngine.forward).
 ``JpegCompressor`` / ``JpegDecompressor`` (:94-128: the uint8 bottleneck image through a JPEG file)
 and ``DataLogger`` (:58-91: pickled sizes of the bottleneck for the reference's cost analysis) are host-side file /
 bookkeeping utilities: the quantisation they contain runs on the same HIP kernel, the rest is PIL / pickle as in the
@@ -322,8 +324,42 @@ class Dequantizer(object):
         return attach(z, out), target
 
 
+FAKE_QUANT_BITS = tuple(range(1, 9))
+
+
+def check_fake_quant_bits(who, num_bits):
+    """the widths the fake-quantising launch (include/hnd_qat.h) takes; anything else is refused by name"""
+    if isinstance(num_bits, bool) or not isinstance(num_bits, int) or num_bits not in FAKE_QUANT_BITS:
+        raise ValueError('%s: num_bits=%r is outside 1 ... 8, the widths the fake-quantised bottleneck implements '
+                         '(16 is the half round trip of Quantizer(16))' % (who, num_bits))
+    return num_bits
+
+
+class FakeQuantizer(object):
+    """``[Quantizer(num_bits), Dequantizer(num_bits)]`` as ONE codec call (include/hnd_qat.h): z -> the dequantised tensor,
+    bit for bit what the pair returns, written back into z's buffer.  1 ... 8 bits; an extension (the reference has no
+    such class).  ``qparams`` holds {min, max, scale, zero_point} of the newest call, on the device."""
+
+    def __init__(self, num_bits=8):
+        self.num_bits = check_fake_quant_bits('FakeQuantizer', num_bits)
+        self._bufs = {}
+        self.qparams = None
+
+    def __call__(self, z, target):
+        buf = to_nhwc(z)                    # [N, H, W, cs] fp32 bottleneck (pad channels are 0)
+        if buf.device not in self._bufs:
+            self._bufs[buf.device] = (torch.empty(4, dtype=torch.float32, device=buf.device),
+                                      torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
+        self.qparams, scratch = self._bufs[buf.device]
+        c = z.shape[1]
+        ops.fake_quantize_bits(buf, c, self.num_bits, self.qparams, scratch)
+        if getattr(z, '_hnd', None) is buf:         # a HIP-path tensor: a view of the buffer just rewritten
+            return z, target
+        return attach(buf[..., :c].permute(0, 3, 1, 2), buf), target
+
+
 TRANSFORMER_CLASS_DICT = {'jpeg_compressor': JpegCompressor, 'jpeg_decompressor': JpegDecompressor,
-                          'quantizer': Quantizer, 'dequantizer': Dequantizer}
+                          'quantizer': Quantizer, 'dequantizer': Dequantizer, 'fake_quantizer': FakeQuantizer}
 
 
 def get_bottleneck_transformer(transformer_config):
