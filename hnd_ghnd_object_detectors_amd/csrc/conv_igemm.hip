@@ -598,17 +598,18 @@ ConvPick pick_conv(const hnd_conv_desc& d) {
   return {TILED, pick_tile(d)};
 }
 
-// hnd_conv2d_igemm_tile's code (include/hnd_hip.h) by kernel and variant; -1: no such variant.  10 is unused.
+// hnd_conv2d_igemm_tile's answer (hnd_conv_tile, include/hnd_hip.h) by kernel and variant; -1: no such variant.
 int tile_code(ConvPick p) {
   static const signed char code[CONV_KERNELS][5] = {
-      /* STEM7     */ {9, -1, -1, -1, -1},
-      /* CIN4_TILE */ {1, -1, -1, -1, -1},
-      /* THIN_N    */ {4, -1, -1, -1, -1},
-      /* BX3       */ {13, 13, 13, -1, -1},      // one code for both builds (hnd_conv2d_igemm_build tells them apart)
-      /* BXS       */ {-1, 15, 14, -1, -1},
-      /* BRES      */ {-1, 6, 5, 8, 7},
-      /* BSTREAM   */ {-1, 12, 11, -1, -1},
-      /* TILED     */ {0, 1, 2, 3, -1}};
+      /* STEM7     */ {HND_TILE_STEM7_LDS, -1, -1, -1, -1},
+      /* CIN4_TILE */ {HND_TILE_IGEMM_128X64, -1, -1, -1, -1},
+      /* THIN_N    */ {HND_TILE_THIN_N4, -1, -1, -1, -1},
+      // one code for both builds (hnd_conv2d_igemm_build tells them apart)
+      /* BX3       */ {HND_TILE_BX3_64, HND_TILE_BX3_64, HND_TILE_BX3_64, -1, -1},
+      /* BXS       */ {-1, HND_TILE_BXS_64, HND_TILE_BXS_128, -1, -1},
+      /* BRES      */ {-1, HND_TILE_BRES_64, HND_TILE_BRES_128, HND_TILE_BRES2_64, HND_TILE_BRES2_128},
+      /* BSTREAM   */ {-1, HND_TILE_BSTREAM_64, HND_TILE_BSTREAM_128, -1, -1},
+      /* TILED     */ {HND_TILE_IGEMM_128X128, HND_TILE_IGEMM_128X64, HND_TILE_IGEMM_64X128, HND_TILE_IGEMM_64X64, -1}};
   return code[p.kernel][p.variant];
 }
 int build_code(ConvPick p) { return p.kernel == BX3 && p.variant ? 1 : 0; }

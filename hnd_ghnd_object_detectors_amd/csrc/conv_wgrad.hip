@@ -418,20 +418,19 @@ int launch_wgrad_ring(const hnd_wgrad_desc& d, int& splits, int& co_pad, int& nc
 
 namespace {
 
-// The partial-sum kernel of a weight gradient, decided once for hnd_conv2d_wgrad and hnd_conv2d_wgrad_variant (whose codes
-// these are).
-enum WgradKernel { WG_STAGED = 0, WG_STEM7 = 1, WG_THIN = 2, WG_RING = 3 };
+// The partial-sum kernel of a weight gradient, decided once for hnd_conv2d_wgrad and hnd_conv2d_wgrad_variant (whose answer
+// it is: hnd_wgrad_variant, include/hnd_hip.h).
 struct WgradPick {
-  WgradKernel kernel;
-  bool thick_is_x;      // WG_THIN: which operand has the 64 channels
+  hnd_wgrad_variant kernel;
+  bool thick_is_x;      // HND_WGRAD_THIN_WGRAD: which operand has the 64 channels
 };
 
 WgradPick pick_wgrad(const hnd_wgrad_desc& d) {
   bool tx = false;
-  if (hnd::stem7_wgrad_applies(d)) return {WG_STEM7, false};
-  if (thin_wgrad_applies(d, tx)) return {WG_THIN, tx};
-  if (hnd::wgrad_ring_applies(d)) return {WG_RING, false};
-  return {WG_STAGED, false};
+  if (hnd::stem7_wgrad_applies(d)) return {HND_WGRAD_STEM7_WGRAD, false};
+  if (thin_wgrad_applies(d, tx)) return {HND_WGRAD_THIN_WGRAD, tx};
+  if (hnd::wgrad_ring_applies(d)) return {HND_WGRAD_WGRAD_RING, false};
+  return {HND_WGRAD_STAGED, false};
 }
 
 }  // namespace
@@ -480,12 +479,12 @@ extern "C" int hnd_conv2d_wgrad(const hnd_wgrad_desc* desc, void* stream) {
   long long group_stride = (long long)d.dw_group_stride;
   const char* reduce = "hnd_conv2d_wgrad(reduce)";
   switch (p.kernel) {
-    case WG_STEM7:
+    case HND_WGRAD_STEM7_WGRAD:
       rc = hnd::launch_stem7_wgrad(d, a.ncols_pad, s);
       splits = hnd::stem7_wgrad_blocks(d); co_pad = 64; ncols_pad = a.ncols_pad; rgroups = 1; group_stride = 0;
       reduce = "hnd_conv2d_wgrad(stem7 reduce)";
       break;
-    case WG_THIN: {
+    case HND_WGRAD_THIN_WGRAD: {
       const bool thick_is_x = p.thick_is_x;
       ThinWgradArgs t;
       t.d = d;
@@ -502,7 +501,7 @@ extern "C" int hnd_conv2d_wgrad(const hnd_wgrad_desc* desc, void* stream) {
       reduce = "hnd_conv2d_wgrad(thin reduce)";
       break;
     }
-    case WG_RING:
+    case HND_WGRAD_WGRAD_RING:
       rc = hnd::launch_wgrad_ring(d, splits, co_pad, ncols_pad, s);
       reduce = "hnd_conv2d_wgrad(ring reduce)";
       break;

@@ -14,6 +14,8 @@ from . import _lib
 from ._lib import ConvDesc, WgradDesc, MsePair, MimicPair, MIMIC_KINDS, check
 
 _L = _lib.load()
+TILE_NAMES = {code: name for name, code in _lib.CONV_TILES.items()}          # enum hnd_conv_tile
+WGRAD_NAMES = {code: name for name, code in _lib.WGRAD_VARIANTS.items()}     # enum hnd_wgrad_variant
 # advanced by every fused optimizer step: packed-weight caches (engine.weight_version) key on it because the raw-pointer
 # parameter update does not touch torch's tensor version counter
 PARAM_EPOCH = [0]
@@ -260,12 +262,10 @@ class ConvLaunch(object):
             self.relay = torch.zeros((need + 3) // 4, dtype=torch.float32, device=torch.device('cuda', torch.cuda.current_device()))
             self.desc.relay_ws = self.relay.data_ptr()
         tile = _L.hnd_conv2d_igemm_tile(self.ref)
-        self.variant = ('stem7_lds' if tile == 9 else 'igemm_c4_128x64') if self.desc.cin == 4 else \
-            ('igemm_128x128', 'igemm_128x64', 'igemm_64x128', 'igemm_64x64', 'thin_n4', 'bres_128',
-             'bres_64', 'bres2_128', 'bres2_64', 'stem7_lds', 'unused', 'bstream_128', 'bstream_64', 'bx3_64',
-             'bxs_128', 'bxs_64')[tile]
+        name = TILE_NAMES[tile]
+        self.variant = name if self.desc.cin != 4 or name == 'stem7_lds' else 'igemm_c4_128x64'
         # which build of that kernel (the emulation kernel has two that give the same bits); None: no such distinction
-        self.build = ('persistent', 'tiled')[int(_L.hnd_conv2d_igemm_build(self.ref))] if tile == 13 else None
+        self.build = ('persistent', 'tiled')[int(_L.hnd_conv2d_igemm_build(self.ref))] if name == 'bx3_64' else None
 
     def run(self, stream=None):
         rc = _L.hnd_conv2d_igemm(self.ref, stream if stream is not None else stream_ptr())
@@ -430,8 +430,8 @@ class WgradLaunch(object):
         self.alg_flops = flops
         self.ref = C.byref(desc)
         # which kernel hnd_conv2d_wgrad dispatches to (asked of the library: csrc/conv_wgrad.hip)
-        self.variant = {1: 'stem7_wgrad', 2: 'thin_wgrad', 3: 'wgrad_ring'}.get(
-            int(_L.hnd_conv2d_wgrad_variant(self.ref)), 'wgrad_m128' if desc.cout >= 128 else 'wgrad_m64')
+        name = WGRAD_NAMES[int(_L.hnd_conv2d_wgrad_variant(self.ref))]
+        self.variant = name if name != 'staged' else 'wgrad_m128' if desc.cout >= 128 else 'wgrad_m64'
 
     def run(self, stream=None):
         rc = _L.hnd_conv2d_wgrad(self.ref, stream if stream is not None else stream_ptr())

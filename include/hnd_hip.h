@@ -155,18 +155,35 @@ typedef struct hnd_conv_desc {
 int hnd_conv2d_igemm(const hnd_conv_desc* desc, void* stream);
 /* bytes of relay_ws this launch can use (0: none -- the field is ignored) */
 size_t hnd_conv2d_igemm_workspace(const hnd_conv_desc* desc);
-/* which block tile the launch above would use: 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64 (pixels x channels),
- * 4 = the vector-ALU kernel for cout <= 4 (one thread per pixel; bit-identical to the MFMA tiles),
- * 5 / 6 = the B-resident persistent GEMM (csrc/conv_bres.hip) with a 128- / 64-column weight slice held in LDS: 1x1
- * taps, K <= 256 / 512, no statistics; bit-identical to the tiled kernel.  HND_BRES=0 in the environment turns it off;
- * 7 / 8 = its one-wave-per-SIMD build (plain epilogues); 9 = the 7x7 stride-2 stem from an LDS-staged input patch
- * (csrc/conv_stem.hip; bit-identical to the generic 4-channel-input kernel, HND_STEM7=0 turns it off); 10 = unused
- * (a K = 1024 build of the one-wave kernel, removed in round 4); 11 / 12 = the B-streamed persistent GEMM for long K
- * (csrc/conv_bstream.hip: 128 x 128 / 256 x 64 block tile, the weight slice streams through three LDS stages, A
- * fragments straight from global memory; K % 128 == 0, K >= 1024 or taps; bit-identical to the tiled kernel;
- * HND_BSTREAM=0 turns it off). */
-int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc);      /* (13 = the bf16x3 emulation kernel, csrc/conv_bx3.hip; 14 / 15 =
-                                                             * its B-streamed build, 128 x 128 / 256 x 64 tile, csrc/conv_bxs.hip) */
+/* which block tile the launch above would use (the lower-cased enumerator without HND_TILE_ is the name the Python host,
+ * the benchmark and the recorded profiles use for the kernel) */
+typedef enum hnd_conv_tile {
+  HND_TILE_IGEMM_128X128 = 0,   /* 0 = 128x128, 1 = 128x64, 2 = 64x128, 3 = 64x64 (pixels x channels) */
+  HND_TILE_IGEMM_128X64 = 1,
+  HND_TILE_IGEMM_64X128 = 2,
+  HND_TILE_IGEMM_64X64 = 3,
+  HND_TILE_THIN_N4 = 4,         /* the vector-ALU kernel for cout <= 4 (one thread per pixel; bit-identical to the MFMA tiles) */
+  /* 5 / 6 = the B-resident persistent GEMM (csrc/conv_bres.hip) with a 128- / 64-column weight slice held in LDS: 1x1
+   * taps, K <= 256 / 512, no statistics; bit-identical to the tiled kernel.  HND_BRES=0 in the environment turns it off;
+   * 7 / 8 = its one-wave-per-SIMD build (plain epilogues) */
+  HND_TILE_BRES_128 = 5,
+  HND_TILE_BRES_64 = 6,
+  HND_TILE_BRES2_128 = 7,
+  HND_TILE_BRES2_64 = 8,
+  /* 9 = the 7x7 stride-2 stem from an LDS-staged input patch (csrc/conv_stem.hip; bit-identical to the generic
+   * 4-channel-input kernel, HND_STEM7=0 turns it off) */
+  HND_TILE_STEM7_LDS = 9,
+  HND_TILE_UNUSED = 10,         /* 10 = unused (a K = 1024 build of the one-wave kernel, removed in round 4) */
+  /* 11 / 12 = the B-streamed persistent GEMM for long K (csrc/conv_bstream.hip: 128 x 128 / 256 x 64 block tile, the
+   * weight slice streams through three LDS stages, A fragments straight from global memory; K % 128 == 0, K >= 1024 or
+   * taps; bit-identical to the tiled kernel; HND_BSTREAM=0 turns it off) */
+  HND_TILE_BSTREAM_128 = 11,
+  HND_TILE_BSTREAM_64 = 12,
+  HND_TILE_BX3_64 = 13,         /* 13 = the bf16x3 emulation kernel, csrc/conv_bx3.hip */
+  HND_TILE_BXS_128 = 14,        /* 14 / 15 = its B-streamed build, 128 x 128 / 256 x 64 tile, csrc/conv_bxs.hip */
+  HND_TILE_BXS_64 = 15
+} hnd_conv_tile;
+int hnd_conv2d_igemm_tile(const hnd_conv_desc* desc);      /* a hnd_conv_tile; -1 on NULL */
 /* which BUILD of the kernel named by hnd_conv2d_igemm_tile runs this launch: 0 = the only / the persistent build, 1 = the
  * tiled build of the bf16x3 emulation kernel (tile 13, csrc/conv_bx3_tiled.hip: one workgroup per output tile, chosen where
  * the persistent kernel's teams would get few 64-row chunks -- small batches, coarse maps); -1 on NULL.  GUARANTEE: both
@@ -220,13 +237,18 @@ typedef struct hnd_wgrad_desc {
 
 size_t hnd_conv2d_wgrad_workspace(const hnd_wgrad_desc* desc);
 int hnd_conv2d_wgrad(const hnd_wgrad_desc* desc, void* stream);
-/* which kernel the launch above would use: 0 = the LDS-staged split-K kernel (csrc/conv_wgrad.hip), 1 = the 7x7 stem from
- * an LDS patch (csrc/conv_stem.hip), 2 = the vector-ALU kernel of the two 3-channel gradients, 3 = the ring kernel
- * (csrc/conv_wgrad_ring.hip: cout % 128 == 0, cin % 64 == 0; both operands straight from global memory through a
- * counted register ring, accumulators resident; by default the 1x1 / grouped Winograd-domain form only;
- * HND_WGRAD_RING=0 turns it off, =2 also takes the tap form).  All sum their split-K slabs in a fixed
- * order: each is bitwise reproducible; different kernels differ in rounding. */
-int hnd_conv2d_wgrad_variant(const hnd_wgrad_desc* desc);
+/* which kernel the launch above would use.  All sum their split-K slabs in a fixed order: each is bitwise reproducible;
+ * different kernels differ in rounding. */
+typedef enum hnd_wgrad_variant {
+  HND_WGRAD_STAGED = 0,         /* 0 = the LDS-staged split-K kernel (csrc/conv_wgrad.hip) */
+  HND_WGRAD_STEM7_WGRAD = 1,    /* 1 = the 7x7 stem from an LDS patch (csrc/conv_stem.hip) */
+  HND_WGRAD_THIN_WGRAD = 2,     /* 2 = the vector-ALU kernel of the two 3-channel gradients */
+  /* 3 = the ring kernel (csrc/conv_wgrad_ring.hip: cout % 128 == 0, cin % 64 == 0; both operands straight from global
+   * memory through a counted register ring, accumulators resident; by default the 1x1 / grouped Winograd-domain form only;
+   * HND_WGRAD_RING=0 turns it off, =2 also takes the tap form) */
+  HND_WGRAD_WGRAD_RING = 3
+} hnd_wgrad_variant;
+int hnd_conv2d_wgrad_variant(const hnd_wgrad_desc* desc);   /* a hnd_wgrad_variant; -1 on NULL */
 
 /* Re-layout torch OIHW weights [cout][cin][kh][kw] into the K-contiguous GEMM operand of
  * hnd_conv2d_igemm.  transposed=0: rows=cout, K=(tap, cin_pad) (forward);  transposed=1: rows=cin,
@@ -563,7 +585,7 @@ int hnd_comm_destroy(void* comm);
  *   proposals[n][anchors_per_image][4] at level_offset in (y, x, a) order (concat_box_prediction_layers), where the
  *   anchor is base_anchors[a] (HOST pointer, A x 4 floats: AnchorGenerator.generate_anchors) + (x*stride_w, y*stride_h)
  *   and the box is BoxCoder(1,1,1,1).decode_single with dw, dh clamped to xform_clip = log(1000/16). */
-int hnd_rpn_decode(const float* head, int n, int h, int w, int ldc, int num_anchors, const float* base_anchors,
+int hnd_rpn_decode(const float* head, int n, int h, int w, int ldc, int num_anchors, const float base_anchors[],
                    float stride_h, float stride_w, int64_t level_offset, int64_t anchors_per_image, float xform_clip,
                    float* objectness, float* proposals, void* stream);
 /* clip_boxes_to_image: x to [0, width], y to [0, height], in place; boxes [n][4] */

@@ -1,6 +1,6 @@
 """The forward / data-gradient wall: the case tables, the fp64 reference and the bars shared by tests/test_conv_cases_cpu.py
 (routing, coverage conditions, the reference against itself: no GPU) and tests/test_conv_gpu.py (the launches).  Nothing
-here imports the library or touches a device; both files read the SAME tuples, so a geometry the CPU file routed is the one
+here loads the library or touches a device; both files read the SAME tuples, so a geometry the CPU file routed is the one
 the GPU runs.
 
 hnd_conv2d_igemm dispatches to eight native kernels (csrc/conv_igemm.hip: pick_conv): the tiled kernel in four block tiles,
@@ -15,16 +15,15 @@ import random
 import torch
 import torch.nn.functional as F
 
+from hnd_ghnd_object_detectors_amd._lib import CONV_TILES         # enum hnd_conv_tile of include/hnd_hip.h (no library is loaded)
 from tests.wgrad_util import ALL_FORMS, PRO_FORMS, SCALE_RELU
 
 U = 2.0 ** -24                                      # unit roundoff of fp32
 PAD_LANE_VALUE = 3.0e4
 SWITCHES = ('HND_BRES', 'HND_BRES2', 'HND_BSTREAM', 'HND_THIN_N', 'HND_STEM7', 'HND_DEBUG_PICKER')
-TILE_NAMES = ('igemm_128x128', 'igemm_128x64', 'igemm_64x128', 'igemm_64x64')
-# ConvLaunch.variant -> hnd_conv2d_igemm_tile's code (include/hnd_hip.h)
-TILE_CODE = {'igemm_128x128': 0, 'igemm_128x64': 1, 'igemm_64x128': 2, 'igemm_64x64': 3, 'thin_n4': 4, 'bres_128': 5,
-             'bres_64': 6, 'bres2_128': 7, 'bres2_64': 8, 'stem7_lds': 9, 'bstream_128': 11, 'bstream_64': 12,
-             'igemm_c4_128x64': 1}
+TILE_NAMES = tuple(sorted((n for n in CONV_TILES if n.startswith('igemm_')), key=CONV_TILES.get))      # the four block tiles, codes 0..3
+# ConvLaunch.variant -> hnd_conv2d_igemm_tile's code: the 4-lane kernel answers with its 128x64 tile
+TILE_CODE = dict(CONV_TILES, igemm_c4_128x64=CONV_TILES['igemm_128x64'])
 KERNELS = ('tiled', 'igemm_c4_128x64', 'stem7_lds', 'thin_n4', 'bres', 'bres2', 'bstream')
 EPI_OPERANDS = ('es', 'eb', 'r1', 'r2', 'up', 'mask', 'relu', 'stats', 'mout')
 COMPUTE_UNITS = 256                                 # what the pickers assume without a device, and what an MI355X has

@@ -37,13 +37,15 @@ NO_OPS = ('HND_BRES2=1', 'HND_BSTREAM=1', 'HND_BXS=1', 'HND_STEM7=1', 'HND_THIN_
 CONV_ANSWERS = ('conv_tile', 'conv_build', 'conv_workspace')
 WGRAD_ANSWERS = ('wgrad_variant', 'wgrad_workspace')
 REC_ANSWERS = ('rec_bx3', 'rec_bxs')
-TILE_CODES = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 14, 15)        # include/hnd_hip.h; 10 is unused
 
 
 def _lib_module():
     sys.path.insert(0, ROOT)
     from hnd_ghnd_object_detectors_amd import _lib
     return _lib
+
+
+TILE_CODES = tuple(sorted(c for n, c in _lib_module().CONV_TILES.items() if n != 'unused'))      # enum hnd_conv_tile
 
 
 def field_names(cls):

@@ -211,16 +211,12 @@ def test_bxs_with_the_relay_is_exact(ops, lib, monkeypatch):
 
 
 # -------------------------------------------------------------------------------- the native family on the same operands
-def _tile_name(tile):
-    return ('igemm_128x128', 'igemm_128x64', 'igemm_64x128', 'igemm_64x64')[tile]
-
-
 @pytest.mark.parametrize('tile', [0, 1, 2, 3])
 @pytest.mark.parametrize('kdim', U.NATIVE_KS)
 def test_native_tiled_kernel_is_exact_on_every_block_tile(ops, monkeypatch, kdim, tile):
     set_env(monkeypatch, HND_DEBUG_PICKER='igemm_tile=%d' % tile, HND_THIN_N='0', **NO_PERSISTENT)
-    wrong = check_set(ops, gemm_set(U.NATIVE_M, kdim, U.NATIVE_COUT), 'off', _tile_name(tile), 'native K %d' % kdim)
-    wrong += check_set(ops, tap_set(U.NATIVE_TAP_CASE), 'off', _tile_name(tile), 'native 3x3 stride 2')
+    wrong = check_set(ops, gemm_set(U.NATIVE_M, kdim, U.NATIVE_COUT), 'off', ops.TILE_NAMES[tile], 'native K %d' % kdim)
+    wrong += check_set(ops, tap_set(U.NATIVE_TAP_CASE), 'off', ops.TILE_NAMES[tile], 'native 3x3 stride 2')
     assert not wrong, '\n'.join(wrong[:8])
 
 

@@ -27,20 +27,14 @@ def built():
     g.build()
 
 
-def _declared():
-    text = re.sub(r'/\*.*?\*/', '', open(HEADER).read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(hnd_[a-z0-9_]+)\s*\(', text)))
-
-
 # ------------------------------------------------------------------------------------------ C ABI
 def test_qat_symbols_resolve_and_the_other_tables_do_not_move():
+    """(that no header's names are in another's tuple: tests/test_lib_cpu.py, over all four headers)"""
     from hnd_ghnd_object_detectors_amd import _lib
     lib = _lib.load()
-    assert list(_lib.QAT_SYMBOLS) == _declared() == ['hnd_fake_quantize_bits', 'hnd_fake_quantize_tiles', 'hnd_qat_abi']
+    assert list(_lib.QAT_SYMBOLS) == ['hnd_fake_quantize_bits', 'hnd_fake_quantize_tiles', 'hnd_qat_abi']
     for name in _lib.QAT_SYMBOLS:
-        fn = getattr(lib, name)
-        assert fn.argtypes is not None
-        assert name not in _lib.EXPORTED_SYMBOLS and name not in _lib.CODEC_SYMBOLS and name not in _lib.OPTIM_SYMBOLS
+        assert getattr(lib, name).argtypes is not None
     header = open(HEADER).read()
     value = int(re.search(r'#define HND_QAT_ABI (\d+)\b', header).group(1))
     assert lib.hnd_qat_abi() == _lib.QAT_ABI == value == 1

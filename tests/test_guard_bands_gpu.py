@@ -13,12 +13,10 @@ The GEMM, conv and weight-gradient families are deterministic and placement-inde
 so their guarded output must also be torch.equal to the same launch on ordinary buffers.
 
 Every case declares the exports it covers (@covers) and records the kernel variant that ran; the last test of the file
-holds the union of variants to the name list of ops.ConvLaunch.refresh_variant, tests/test_guard_ledger_cpu.py holds the
+holds the union of variants to the names of the header's enums (ops.TILE_NAMES, ops.WGRAD_NAMES), tests/test_guard_ledger_cpu.py holds the
 union of exports, with NO_DEVICE_OUTPUT, to the header.  Importing this module does not touch the GPU.
 """
-import inspect
 import math
-import re
 
 import pytest
 import torch
@@ -381,7 +379,8 @@ def _tile_name(tile, cout, stats=False, mask_out=False):
         tile -= 2
     if mask_out and tile in (1, 3):
         tile -= 1
-    return ('igemm_128x128', 'igemm_128x64', 'igemm_64x128', 'igemm_64x64')[tile]
+    from hnd_ghnd_object_detectors_amd._lib import CONV_TILES
+    return {code: name for name, code in CONV_TILES.items()}[tile]             # enum hnd_conv_tile
 
 
 @covers('hnd_conv2d_igemm')
@@ -1661,13 +1660,12 @@ def test_mask_and_keypoint_branch_operators(ops, lib):
 # ------------------------------------------------------------------------------------------------- variant coverage
 def test_every_kernel_variant_ran_under_guards(ops):
     """LAST in the file: the union of variants that ran inside an arena equals every name ConvLaunch.refresh_variant can
-    give (minus 'unused') plus the weight-gradient kernels plus both builds of the emulation kernel -- a kernel added
+    give (enum hnd_conv_tile minus 'unused', and the 4-lane tile) plus the weight-gradient kernels plus both builds of the emulation kernel -- a kernel added
     later without a guard case turns this red.  RAN is filled by the cases above IN THIS PROCESS: the test needs the whole
     file in one run and fails under -k, --lf, a node id of its own or pytest-xdist."""
-    src = inspect.getsource(ops.ConvLaunch.refresh_variant)
-    stmt = src[src.index('self.variant ='):src.index('[tile]')]
-    names = set(re.findall(r"'([^']+)'", stmt)) - {'unused'}
+    names = (set(ops.TILE_NAMES.values()) - {'unused'}) | {'igemm_c4_128x64'}      # enum hnd_conv_tile and the 4-lane special case
     assert len(names) >= 16, sorted(names)
     expect = (names - {'bx3_64'}) | {'bx3_64/persistent', 'bx3_64/tiled'}
-    expect |= {'wgrad_m64', 'wgrad_m128', 'stem7_wgrad', 'thin_wgrad', 'wgrad_ring'}
+    expect |= (set(ops.WGRAD_NAMES.values()) - {'staged'}) | {'wgrad_m64', 'wgrad_m128'}      # enum hnd_wgrad_variant
+    assert expect >= {'wgrad_m64', 'wgrad_m128', 'stem7_wgrad', 'thin_wgrad', 'wgrad_ring'}
     assert RAN == expect, (sorted(expect - RAN), sorted(RAN - expect))

@@ -1,12 +1,23 @@
-"""CPU: the C-ABI library builds, loads, and exports every symbol include/hnd_hip.h declares."""
+"""CPU: the C-ABI library builds, loads, and exports every symbol the four headers under include/ declare; the binding
+hnd_ghnd_object_detectors_amd/_lib.py reads from those headers lays its structs out as the C compiler does, and its reader
+refuses what it does not know."""
+import ctypes
 import os
 import re
+import shutil
+import subprocess
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER_NAMES = ('hnd_hip.h', 'hnd_optim.h', 'hnd_codec.h', 'hnd_qat.h')
+STRUCTS = {'hnd_conv_desc': 'ConvDesc', 'hnd_wgrad_desc': 'WgradDesc', 'hnd_pack_desc': 'PackDesc', 'hnd_image_desc': 'ImageDesc',
+           'hnd_boxes_desc': 'BoxesDesc', 'hnd_mse_pair': 'MsePair', 'hnd_mimic_pair': 'MimicPair', 'hnd_optim_desc': 'OptimDesc'}
 
 
-def _declared():
-    text = open(os.path.join(ROOT, 'include', 'hnd_hip.h')).read()
+def _declared(header='hnd_hip.h'):
+    """the names a header declares, found WITHOUT the reader of _lib.py"""
+    text = open(os.path.join(ROOT, 'include', header)).read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     return sorted(set(re.findall(r'\b(hnd_[a-z0-9_]+)\s*\(', text)))
 
@@ -24,15 +35,72 @@ def test_library_exports_every_declared_symbol():
     assert lib.hnd_abi_version() == _lib.ABI_VERSION == 12
 
 
-def test_ctypes_structs_match_header_layout():
+def test_every_export_is_declared_by_exactly_one_header():
+    """the optimizer kinds, the bit codec and the fake quantiser came with a header, a version and a symbol tuple of their
+    own: no name of theirs is in another header's tuple, and hnd_hip.h still declares exactly the 94 it did"""
+    import __graft_entry__ as g
+    g.build()
     from hnd_ghnd_object_detectors_amd import _lib
-    import ctypes
-    assert ctypes.sizeof(_lib.ConvDesc) == 11 * 8 + 30 * 4 + 3 * 8 + 5 * 8 + 8 + 8 + 8      # (+ w_bf16x3, ABI 10; + w_bf16x3s, ABI 12)
-    assert ctypes.sizeof(_lib.WgradDesc) == 6 * 8 + 16 * 4 + 3 * 8
-    assert ctypes.sizeof(_lib.MsePair) == 3 * 8 + 8 + 4 + 4
-    assert ctypes.sizeof(_lib.ImageDesc) == 8 + 7 * 4 + 2 * 4 + 4        # hnd_image_desc (padded to 8)
-    assert ctypes.sizeof(_lib.BoxesDesc) == 2 * 8 + 4 + 2 * 4 + 4          # hnd_boxes_desc (padded to 8)
-    assert ctypes.sizeof(_lib.PackDesc) == 2 * 8 + 12 * 4                  # hnd_pack_desc
+    lib = _lib.load()
+    tuples = dict(zip(HEADER_NAMES, (_lib.EXPORTED_SYMBOLS, _lib.OPTIM_SYMBOLS, _lib.CODEC_SYMBOLS, _lib.QAT_SYMBOLS)))
+    assert tuple(_lib.HEADERS) == HEADER_NAMES
+    for header, names in tuples.items():
+        assert list(names) == _declared(header) == sorted(_lib.HEADERS[header].functions), header
+    every = [n for names in tuples.values() for n in names]
+    assert len(every) == len(set(every)) == 104 and [len(tuples[h]) for h in HEADER_NAMES] == [94, 2, 5, 3]
+    for name in every:
+        assert getattr(lib, name).argtypes is not None, name
+
+
+def test_ctypes_structs_match_header_layout(tmp_path):
+    """sizeof of the eight structs and offsetof of every field, printed by a host C program compiled from the four headers
+    with the ROCm toolchain's compiler (no device code), against the classes _lib.py generates"""
+    from hnd_ghnd_object_detectors_amd import _lib
+    assert {tag for h in _lib.HEADERS.values() for tag in h.structs} == set(STRUCTS)
+    lines = ['#include <stddef.h>', '#include <stdio.h>'] + ['#include "%s"' % h for h in HEADER_NAMES] + ['int main(void) {']
+    want = {}
+    for tag, cls in ((tag, getattr(_lib, name)) for tag, name in STRUCTS.items()):
+        assert cls is [h for h in _lib.HEADERS.values() if tag in h.structs][0].structs[tag]
+        lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (tag, tag))
+        want[tag] = ctypes.sizeof(cls)
+        for field, _ in cls._fields_:
+            lines.append('  printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (tag, field, tag, field))
+            want['%s.%s' % (tag, field)] = getattr(cls, field).offset
+    (tmp_path / 'layout.c').write_text('\n'.join(lines + ['  return 0;', '}', '']))
+    hipcc = os.environ.get('HIPCC') or shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    subprocess.run([hipcc, '-std=c99', '-Wall', '-Werror', '-I' + os.path.join(ROOT, 'include'), str(tmp_path / 'layout.c'), '-o',
+                    str(tmp_path / 'layout')], check=True, capture_output=True, text=True, timeout=300)
+    out = subprocess.run([str(tmp_path / 'layout')], check=True, capture_output=True, text=True, timeout=60).stdout
+    got = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    assert len(want) == 8 + sum(len(getattr(_lib, name)._fields_) for name in STRUCTS.values()) and len(want) > 140
+    assert got == want, sorted(set(got.items()) ^ set(want.items()))
+
+
+@pytest.mark.parametrize('snippet, line', [
+    ('int hnd_f(long n);', 1),                                                       # an unknown type
+    ('int hnd_f(const float* x,\n          unsigned int n);', 1),
+    ('typedef struct hnd_s {\n  int32_t n;\n  wchar_t* name;\n} hnd_s;', 3),
+    ('\n\nint hnd_f(void (*done)(int), void* stream);', 3),                          # a function-pointer parameter
+    ('int hnd_f(int n);\ntypedef struct hnd_s {\n  int32_t n;\n', 2),               # an unterminated struct
+    ('typedef struct hnd_s {\n  int32_t n\n} hnd_s;', 3),
+    ('typedef struct hnd_s {\n  float *a, b;\n} hnd_s;', 2),
+    ('typedef enum hnd_e {\n  HND_A = 0,\n  HND_B\n} hnd_e;', 3),                   # an enumerator without its value
+    ('#define HND_N 1\n#if HND_N\nint hnd_f(void);\n#endif', 2),
+    ('int hnd_f();', 1),
+    ('/* never closed\nint hnd_f(void);', 1),
+])
+def test_reader_refuses_what_is_outside_its_grammar(snippet, line):
+    from hnd_ghnd_object_detectors_amd import _lib
+    with pytest.raises(_lib.HndLibraryError, match=r'^snippet\.h:%d: ' % line):
+        _lib.parse_header(snippet, 'snippet.h')
+
+
+def test_reader_refuses_a_function_declared_twice():
+    from hnd_ghnd_object_detectors_amd import _lib
+    once = _lib.parse_header('int hnd_f(int n, void* stream);', 'snippet.h')
+    assert once.functions == {'hnd_f': (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p])}
+    with pytest.raises(_lib.HndLibraryError, match=r'^snippet\.h:2: hnd_f is declared twice'):
+        _lib.parse_header('int hnd_f(int n, void* stream);\nint hnd_f(int64_t n, void* stream);', 'snippet.h')
 
 
 def test_invalid_arguments_are_reported_not_thrown():

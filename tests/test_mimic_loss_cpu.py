@@ -86,12 +86,11 @@ def test_criterion_section_with_mixed_terms_parses_and_org_loss_factor_is_still_
 
 # ------------------------------------------------------------------------------------------ C ABI
 def test_mimic_pair_matches_the_header_layout():
+    """(sizeof and every offsetof of both pair structs against the C compiler: tests/test_lib_cpu.py)"""
     from hnd_ghnd_object_detectors_amd import _lib
-    assert ctypes.sizeof(_lib.MimicPair) == 3 * 8 + 2 * 8 + 2 * 4 + 2 * 4      # struct hnd_mimic_pair
     assert [n for n, _ in _lib.MimicPair._fields_] == ['teacher', 'student', 'grad', 'numel', 'count', 'factor', 'param',
                                                       'kind', 'relu_mask']
     assert _lib.MIMIC_KINDS == {'mse': 0, 'l1': 1, 'smooth_l1': 2, 'huber': 3}  # enum hnd_mimic_kind
-    assert ctypes.sizeof(_lib.MsePair) == 3 * 8 + 8 + 4 + 4                     # (untouched)
     assert 'hnd_mimic_loss_fwd_bwd' in _lib.EXPORTED_SYMBOLS
 
 
