@@ -1,6 +1,7 @@
 """ctypes binding of libhnd_hip.so, derived from its C headers: include/hnd_hip.h, hnd_optim.h (the further optimizer
 kinds), hnd_codec.h (the 1 ... 8-bit bottleneck codec) and hnd_qat.h (the fake-quantised bottleneck of the training step),
-each with a version of its own.  parse_header() reads the small grammar those headers use; the struct classes, the enum
+each with a version of its own, and -- beside those four -- hnd_qrange.h (the fixed quantisation range of the bottleneck),
+with a version of its own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
 dictionaries, the ABI numbers, the symbol tuples and every restype / argtypes below come from what it read, so the headers
 are the only place the contract is written down.
 
@@ -142,6 +143,12 @@ WGRAD_VARIANTS = _names(_HIP, 'hnd_wgrad_variant', 'HND_WGRAD_')     # what hnd_
 ABI_VERSION, OPTIM_ABI = _HIP.defines['HND_ABI_VERSION'], _OPTIM.defines['HND_OPTIM_ABI']
 CODEC_ABI, QAT_ABI = _CODEC.defines['HND_CODEC_ABI'], _QAT.defines['HND_QAT_ABI']
 EXPORTED_SYMBOLS, OPTIM_SYMBOLS, CODEC_SYMBOLS, QAT_SYMBOLS = (tuple(sorted(h.functions)) for h in HEADERS.values())
+# the fixed quantisation range: a fifth header, kept beside HEADERS (whose four entries and symbol counts are pinned)
+QRANGE_HEADER_NAME = 'hnd_qrange.h'
+QRANGE_HEADER = _read(QRANGE_HEADER_NAME)
+QRANGE_ABI, QRANGE_SYMBOLS = QRANGE_HEADER.defines['HND_QRANGE_ABI'], tuple(sorted(QRANGE_HEADER.functions))
+if QRANGE_HEADER.structs or QRANGE_HEADER.enums:
+    raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % QRANGE_HEADER_NAME)
 
 _lib = None
 
@@ -161,7 +168,7 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for header in HEADERS.values():
+    for header in list(HEADERS.values()) + [QRANGE_HEADER]:
         for name, (res, args) in header.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -177,6 +184,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so codec ABI %d != expected %d' % (lib.hnd_codec_abi(), CODEC_ABI))
     if lib.hnd_qat_abi() != QAT_ABI:
         raise HndLibraryError('libhnd_hip.so fake-quantisation ABI %d != expected %d' % (lib.hnd_qat_abi(), QAT_ABI))
+    if lib.hnd_qrange_abi() != QRANGE_ABI:
+        raise HndLibraryError('libhnd_hip.so quantisation-range ABI %d != expected %d' % (lib.hnd_qrange_abi(), QRANGE_ABI))
     _lib = lib
     return lib
 

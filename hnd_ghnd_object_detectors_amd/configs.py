@@ -18,21 +18,45 @@ def _term(layer):
 ENCODER_PATH = 'backbone.body.layer1.encoder'
 
 
-def fake_quantize_bits_of(config):
-    """the width of the optional section ``train.fake_quantize: {num_bits: b}`` (quantisation-aware distillation, an
-    extension: the reference has no such key), or None when the section is absent.  Refused by name here, at config time:
-    a width outside 1 ... 8, and a criterion term whose student module is the bottleneck tensor's (layer1.encoder)."""
+FAKE_QUANTIZE_MOMENTUM = 0.01       # default of train.fake_quantize.range.momentum
+
+
+def _fake_quantize_section(config):
+    """(section or None, bits, range dict or None) of ``train.fake_quantize``, with every refusal of its shape"""
     train = config.get('train') or {}
     section = train.get('fake_quantize')
     if section is None:
-        return None
-    if not isinstance(section, dict) or set(section) != {'num_bits'}:
-        raise ValueError('train.fake_quantize must be {num_bits: b}, got %r' % (section,))
+        return None, None, None
+    shape = '{num_bits: b} or {num_bits: b, range: {type: batch}} or {num_bits: b, range: {type: ema, momentum: m}}'
+    if not isinstance(section, dict) or 'num_bits' not in section or not set(section) <= {'num_bits', 'range'}:
+        raise ValueError('train.fake_quantize must be %s, got %r' % (shape, section))
     bits = section['num_bits']
     if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
         raise ValueError('train.fake_quantize.num_bits=%r is outside 1 ... 8, the widths the fake-quantised bottleneck '
                          'implements' % (bits,))
-    terms = ((train.get('criterion') or {}).get('terms') or {})
+    rng = None
+    if 'range' in section:
+        r = section['range']
+        if not isinstance(r, dict) or r.get('type') not in ('batch', 'ema') or \
+                not set(r) <= ({'type', 'momentum'} if r.get('type') == 'ema' else {'type'}):
+            raise ValueError('train.fake_quantize must be %s, got %r' % (shape, section))
+        if r['type'] == 'ema':
+            m = r.get('momentum', FAKE_QUANTIZE_MOMENTUM)
+            if isinstance(m, bool) or not isinstance(m, (int, float)) or not 0 < m <= 1:
+                raise ValueError('train.fake_quantize must be %s with 0 < momentum <= 1, got momentum=%r' % (shape, m))
+            rng = {'momentum': float(m), 'frozen': False}
+    return section, bits, rng
+
+
+def fake_quantize_bits_of(config):
+    """the width of the optional section ``train.fake_quantize: {num_bits: b}`` (quantisation-aware distillation, an
+    extension: the reference has no such key), or None when the section is absent.  Refused by name here, at config time:
+    a width outside 1 ... 8, a malformed section (``range``: see fake_quantize_range_of), and a criterion term whose student
+    module is the bottleneck tensor's (layer1.encoder)."""
+    section, bits, _ = _fake_quantize_section(config)
+    if section is None:
+        return None
+    terms = (((config.get('train') or {}).get('criterion') or {}).get('terms') or {})
     for name, term in terms.items():
         if list(term.get('ts_modules', ()))[1:2] == [ENCODER_PATH]:
             raise NotImplementedError('train.fake_quantize together with the loss term `%s` on %s is not built: the '
@@ -41,12 +65,28 @@ def fake_quantize_bits_of(config):
     return bits
 
 
+def fake_quantize_range_of(config):
+    """``train.fake_quantize.range``: None for no section, no ``range`` key or ``{type: batch}`` (min / max of each batch,
+    include/hnd_qat.h), or ``{'momentum': m, 'frozen': False}`` for ``{type: ema, momentum: m}`` (0 < m <= 1, default
+    0.01): the fixed range of include/hnd_qrange.h, an exponential moving average of the batch min / max"""
+    fake_quantize_bits_of(config)
+    return _fake_quantize_section(config)[2]
+
+
 def make_config(model='faster_rcnn', method='ghnd', bch=3, batch_size=4, pretrained=True, min_size=None,
-                max_size=None, ckpt_root='./resource/ckpt', fake_quantize_bits=None):
+                max_size=None, ckpt_root='./resource/ckpt', fake_quantize_bits=None, fake_quantize_range=None):
+    """fake_quantize_range: None, or the ``range`` section itself ({'type': 'ema', 'momentum': m} / {'type': 'batch'});
+    needs fake_quantize_bits"""
     config = _make_config(model, method, bch, batch_size, pretrained, min_size, max_size, ckpt_root)
+    if fake_quantize_range is not None and fake_quantize_bits is None:
+        raise ValueError('train.fake_quantize must be given num_bits (fake_quantize_bits) for a range %r'
+                         % (fake_quantize_range,))
     if fake_quantize_bits is not None:
         config['train']['fake_quantize'] = {'num_bits': fake_quantize_bits}
-        fake_quantize_bits_of(config)
+        if fake_quantize_range is not None:
+            config['train']['fake_quantize']['range'] = dict(fake_quantize_range) \
+                if isinstance(fake_quantize_range, dict) else fake_quantize_range
+        fake_quantize_range_of(config)
     return config
 
 

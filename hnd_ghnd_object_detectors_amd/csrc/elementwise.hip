@@ -5,11 +5,13 @@
 #include "common.h"
 #include "hnd_codec.h"
 #include "hnd_qat.h"
+#include "hnd_qrange.h"
 
 #include <hip/hip_fp16.h>
 #include <float.h>
 #include <limits.h>
 #include <math.h>
+#include <cmath>
 
 namespace {
 
@@ -1249,12 +1251,18 @@ __global__ void unpack_dequantize_kernel(const uint8_t* __restrict__ payload, co
 // group for the whole tile (64 / groups rows per pass; a pixel wider than 64 groups is walked 64 groups at a time).  The
 // per-lane sums meet in LDS and are added in row-slot order: a fixed order, no atomics.  x and y may be the same buffer
 // (every float is read and written by one lane), so neither is __restrict__.
+// include/hnd_qrange.h builds the same kernel with kMask: qparams are then a caller's fixed range, values may lie outside it,
+// and `mask` (when not null) receives per pixel and group one byte whose bit k says that channel 4 g + k was NOT clipped
+// (rint(u) inside [0, qmax]; false for a NaN) -- one plain byte store per lane beside its 16-byte store of y, a wave's bytes
+// consecutive like its loads.  Pad channels and the high nibble are 0.
 constexpr int kFqRows = HND_FAKE_QUANT_TILE_ROWS;
 constexpr int kFqWaves = 4;
 
+template <bool kMask>
 __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const float* x, float* y, long long npix, int c,
                                                                       int cs, const float* __restrict__ qp, float qmax,
-                                                                      float* __restrict__ stats, int ntiles) {
+                                                                      float* __restrict__ stats, int ntiles,
+                                                                      uint8_t* __restrict__ mask) {
 #pragma clang fp contract(off)
   __shared__ float red[kFqWaves][64][8];
   const float scale = qp[2], zp = qp[3];
@@ -1275,11 +1283,16 @@ __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const floa
           const long long e = (row0 + r) * cs + ch0;
           const f32x4 v = *(const f32x4*)(x + e);
           f32x4 o;
+          unsigned pass = 0;
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             float q = 0.f;
             if (ch0 + k < c) {
               q = __fadd_rn(zp, __fdiv_rn(v[k], scale));            // zero_point + x / scale
+              if (kMask) {
+                const float r = rintf(q);
+                pass |= (r >= 0.f && r <= qmax) ? 1u << k : 0u;    // not clipped (-0 passes, a NaN does not)
+              }
               q = q < 0.f ? 0.f : (q > qmax ? qmax : q);           // clamp_(qmin, qmax)
               q = rintf(q);                                        // round_(): half to even
               q = __fmul_rn(scale, __fsub_rn(q, zp));              // scale * (q - zero_point)
@@ -1289,9 +1302,10 @@ __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const floa
             ss[k] += q * q;
           }
           *(f32x4*)(y + e) = o;
+          if (kMask && mask != nullptr) mask[(row0 + r) * groups + gb + gl] = (uint8_t)pass;
         }
       }
-      if (stats != nullptr) {                                     // (uniform over the block)
+      if (stats != nullptr) {                                    // (uniform over the block)
 #pragma unroll
         for (int k = 0; k < 4; ++k) { red[wave][lane][k] = s[k]; red[wave][lane][4 + k] = ss[k]; }
         __syncthreads();
@@ -1306,6 +1320,64 @@ __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const floa
         __syncthreads();
       }
     }
+  }
+}
+
+// include/hnd_qrange.h: qparams of a range (lo, hi) -- qparams_kernel's formula, operation by operation
+__device__ __forceinline__ void qrange_write_qparams(float lo, float hi, float qmax, float* __restrict__ qp) {
+#pragma clang fp contract(off)
+  const float scale = __fdiv_rn(__fsub_rn(hi, lo), qmax);          // (max - min) / (qmax - qmin), qmin = 0
+  float zp = __fsub_rn(0.f, __fdiv_rn(lo, scale));                 // qmin - min / scale
+  zp = zp < 0.f ? 0.f : (zp > qmax ? qmax : zp);
+  qp[0] = lo; qp[1] = hi; qp[2] = scale; qp[3] = truncf(zp);       // int(zero_point)
+}
+
+// one wave: the batch (lo, hi) from minmax_kernel's partials, folded into state = {running_min, running_max, steps, 0}
+__global__ void qrange_observe_kernel(const float* __restrict__ part, int nblocks, float momentum, float qmax,
+                                      float* __restrict__ state, float* __restrict__ qp) {
+#pragma clang fp contract(off)
+  float lo = INFINITY, hi = -INFINITY;
+  for (int i = threadIdx.x; i < nblocks; i += 64) {
+    lo = fminf(lo, part[i * 2]);
+    hi = fmaxf(hi, part[i * 2 + 1]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  if (threadIdx.x == 0) {
+    float rmin = state[0], rmax = state[1];
+    const float steps = state[2];
+    if (steps == 0.f) {
+      rmin = lo;
+      rmax = hi;
+    } else {
+      rmin = __fadd_rn(rmin, __fmul_rn(momentum, __fsub_rn(lo, rmin)));
+      rmax = __fadd_rn(rmax, __fmul_rn(momentum, __fsub_rn(hi, rmax)));
+    }
+    state[0] = rmin; state[1] = rmax; state[2] = __fadd_rn(steps, 1.f); state[3] = 0.f;
+    qrange_write_qparams(rmin, rmax, qmax, qp);
+  }
+}
+
+__global__ void qrange_qparams_kernel(float lo, float hi, float qmax, float* __restrict__ qp) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) qrange_write_qparams(lo, hi, qmax, qp);
+}
+
+// the backward of the clipping: one thread per 4-channel group (one mask byte, one 16-byte load and store); a clipped real
+// channel gets +0, everything else -- pad channels included -- keeps its bits
+__global__ void qrange_mask_grad_kernel(float* __restrict__ g, const uint8_t* __restrict__ mask, long long ngroups, int c,
+                                        int groups) {
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < ngroups;
+       e += (long long)gridDim.x * blockDim.x) {
+    const int ch0 = (int)(e % groups) * 4;
+    const unsigned m = mask[e];
+    f32x4 v = *(const f32x4*)(g + e * 4);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (ch0 + k < c && !((m >> k) & 1u)) v[k] = 0.f;
+    *(f32x4*)(g + e * 4) = v;
   }
 }
 
@@ -1872,9 +1944,95 @@ int hnd_fake_quantize_bits(const float* x, float* y, int64_t npix, int c, int cs
   launch_qparams(x, (long long)npix, c, cs, qmax, qparams, scratch, s);
   int nb = (ntiles + kFqWaves - 1) / kFqWaves;
   if (nb > kMaxBlocks) nb = kMaxBlocks;
-  hipLaunchKernelGGL(fake_quantize_kernel, dim3(nb), dim3(64 * kFqWaves), 0, s, x, y, (long long)npix, c, cs, qparams,
-                     qmax, stats, ntiles);
+  hipLaunchKernelGGL(fake_quantize_kernel<false>, dim3(nb), dim3(64 * kFqWaves), 0, s, x, y, (long long)npix, c, cs,
+                     qparams, qmax, stats, ntiles, (uint8_t*)nullptr);
   return hnd::check_launch("hnd_fake_quantize_bits");
+}
+
+// ---- include/hnd_qrange.h: the fixed (EMA-calibrated) range
+int hnd_qrange_abi(void) { return HND_QRANGE_ABI; }
+
+static inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
+}
+
+int hnd_qrange_observe(const float* x, int64_t npix, int c, int cs, float momentum, int bits, float* state, float* qparams,
+                       float* scratch, void* stream) {
+  HND_REQUIRE(x && state && qparams && scratch, "hnd_qrange_observe: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_qrange_observe: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_qrange_observe: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
+  HND_REQUIRE(momentum > 0.f && momentum <= 1.f, "hnd_qrange_observe: momentum outside (0, 1]");
+  HND_REQUIRE(aligned16(x, state, qparams), "hnd_qrange_observe: x, state and qparams must be 16-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  int nb = grid_for((long long)npix * cs);
+  if (nb > kMinMaxBlocks) nb = kMinMaxBlocks;
+  hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(256), 0, s, x, (long long)npix, c, cs, scratch);
+  hipLaunchKernelGGL(qrange_observe_kernel, dim3(1), dim3(64), 0, s, scratch, nb, momentum, (float)((1 << bits) - 1), state,
+                     qparams);
+  return hnd::check_launch("hnd_qrange_observe");
+}
+
+int hnd_qrange_qparams(float lo, float hi, int bits, float* qparams, void* stream) {
+  HND_REQUIRE(qparams, "hnd_qrange_qparams: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_qrange_qparams: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "hnd_qrange_qparams: the range needs finite lo < hi");
+  HND_REQUIRE(aligned16(qparams), "hnd_qrange_qparams: qparams must be 16-byte aligned");
+  hipLaunchKernelGGL(qrange_qparams_kernel, dim3(1), dim3(1), 0, hnd::as_stream(stream), lo, hi, (float)((1 << bits) - 1),
+                     qparams);
+  return hnd::check_launch("hnd_qrange_qparams");
+}
+
+int hnd_fake_quantize_range(const float* x, float* y, int64_t npix, int c, int cs, int bits, const float* qparams,
+                            uint8_t* mask, float* stats, void* stream) {
+  HND_REQUIRE(x && y && qparams, "hnd_fake_quantize_range: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_fake_quantize_range: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_fake_quantize_range: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
+  const int ntiles = hnd_fake_quantize_tiles(npix);
+  HND_REQUIRE(ntiles > 0, "hnd_fake_quantize_range: npix too large (the tile count must fit an int)");
+  HND_REQUIRE(aligned16(x, y, qparams), "hnd_fake_quantize_range: x, y and qparams must be 16-byte aligned");
+  int nb = (ntiles + kFqWaves - 1) / kFqWaves;
+  if (nb > kMaxBlocks) nb = kMaxBlocks;
+  hipLaunchKernelGGL(fake_quantize_kernel<true>, dim3(nb), dim3(64 * kFqWaves), 0, hnd::as_stream(stream), x, y,
+                     (long long)npix, c, cs, qparams, (float)((1 << bits) - 1), stats, ntiles, mask);
+  return hnd::check_launch("hnd_fake_quantize_range");
+}
+
+int hnd_qrange_mask_grad(float* g, const uint8_t* mask, int64_t npix, int c, int cs, void* stream) {
+  HND_REQUIRE(g && mask, "hnd_qrange_mask_grad: null pointer");
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_qrange_mask_grad: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
+  HND_REQUIRE(aligned16(g), "hnd_qrange_mask_grad: g must be 16-byte aligned");
+  const long long ngroups = (long long)npix * (cs / 4);
+  hipLaunchKernelGGL(qrange_mask_grad_kernel, dim3(grid_for(ngroups)), dim3(256), 0, hnd::as_stream(stream), g, mask,
+                     ngroups, c, cs / 4);
+  return hnd::check_launch("hnd_qrange_mask_grad");
+}
+
+int hnd_quantize_range_bits(const float* x, int64_t npix, int c, int cs, int bits, uint8_t* q, const float* qparams,
+                            void* stream) {
+  HND_REQUIRE(x && q && qparams, "hnd_quantize_range_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_range_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_quantize_range_bits: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
+  HND_REQUIRE(aligned16(x, qparams), "hnd_quantize_range_bits: x and qparams must be 16-byte aligned");
+  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, hnd::as_stream(stream), x,
+                     (long long)npix, c, cs, qparams, (float)((1 << bits) - 1), q);
+  return hnd::check_launch("hnd_quantize_range_bits");
+}
+
+int hnd_quantize_pack_range_bits(const float* x, int n, int h, int w, int c, int cs, int bits, uint8_t* payload,
+                                 const float* qparams, void* stream) {
+  HND_REQUIRE(x && payload && qparams, "hnd_quantize_pack_range_bits: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_pack_range_bits: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c && cs % 4 == 0,
+              "hnd_quantize_pack_range_bits: bad geometry (n, h, w, c > 0, cs >= c, cs %% 4 == 0)");
+  HND_REQUIRE(aligned16(x, qparams), "hnd_quantize_pack_range_bits: x and qparams must be 16-byte aligned");
+  const long long hw = (long long)h * w, numel = hw * n * c;
+  hipLaunchKernelGGL(quantize_pack_kernel, dim3(grid_for((numel + 7) / 8)), dim3(256), 0, hnd::as_stream(stream), x, numel,
+                     c, hw, cs, bits, qparams, (float)((1 << bits) - 1), payload);
+  return hnd::check_launch("hnd_quantize_pack_range_bits");
 }
 
 int hnd_roundtrip_f16(float* x, int64_t numel, void* stream) {

@@ -681,19 +681,36 @@ class HeadEngine(object):
     def bwd_out_bits(self):
         return getattr(self, 'out_bits', None)
 
-    def forward(self, x, training, codec=None, fake_quant_bits=None):
+    def forward(self, x, training, codec=None, fake_quant_bits=None, fake_quant_range=None):
         """fake_quant_bits (1 ... 8, training only; include/hnd_qat.h): the bottleneck tensor z = y[encoder_len - 1] is
         quantised and dequantised IN PLACE between its conv and its BatchNorm (decoder.0), whose batch statistics then come
         from the launch that stored the quantised values.  The backward plan is NOT changed, on purpose: the estimator is
         straight-through (d z' / d z = 1), so dy of the encoder's last conv is what bn_bwd_apply leaves in g[zi] -- and
         everything that reads y[zi] in the backward (bn_bwd_reduce / bn_bwd_apply, the weight gradient of the decoder's
         first conv) must read the quantised values, which is what the buffer now holds.  No clamping mask is needed:
-        min / max come from the tensor itself, so zero_point + z / scale never leaves [0, qmax] by more than rounding."""
+        min / max come from the tensor itself, so zero_point + z / scale never leaves [0, qmax] by more than rounding.
+
+        fake_quant_range (with fake_quant_bits, training only; include/hnd_qrange.h): {'state': device float[4], 'momentum': m,
+        'frozen': bool, 'range': (lo, hi) or None}.  The quantiser then clips to a FIXED range: qrange_observe folds this
+        batch's min / max into `state` and writes qparams of the running pair (skipped when frozen: qparams of the host
+        pair 'range' are made once, when the plan is built), fake_quantize_range quantises in place in ONE launch and
+        stores the clip mask, and the backward zeroes dy of the encoder's last conv where the value was clipped
+        (qrange_mask_grad on g[zi], after bn_bwd_apply and before anything reads it).  None: nothing in either plan
+        changes."""
         if fake_quant_bits is not None:
             if isinstance(fake_quant_bits, bool) or not isinstance(fake_quant_bits, int) or not 1 <= fake_quant_bits <= 8:
                 raise ValueError('HeadEngine.forward: fake_quant_bits=%r is outside 1 ... 8' % (fake_quant_bits,))
             if not training:
                 fake_quant_bits = None      # (the eval path is the codec's)
+        if fake_quant_bits is None:
+            fake_quant_range = None
+        range_key = None
+        if fake_quant_range is not None:
+            r = fake_quant_range
+            if r['frozen'] and r.get('range') is None:
+                raise ValueError('HeadEngine.forward: a frozen fake_quant_range needs its host pair \'range\'')
+            range_key = (r['state'].data_ptr(), float(r['momentum']), bool(r['frozen']),
+                         tuple(r['range']) if r['frozen'] else None)
         if self.bufs is None:
             self.bufs = Buffers(x.device)
         ops.pack_batch_begin()              # the ~28 operand re-packs of a training step go out as one launch
@@ -708,9 +725,9 @@ class HeadEngine(object):
                      for t in (hc.bn.weight, hc.bn.bias, hc.bn.running_mean, hc.bn.running_var))
         self._out_buf = self.out_provider(self.out_shape(x)) if self.out_provider is not None else None
         key = (x.data_ptr(), tuple(x.shape), training, ptrs, None if self._out_buf is None else self._out_buf.data_ptr(),
-               fake_quant_bits)
+               fake_quant_bits) + (() if range_key is None else (range_key,))
         if key != self.plan_key:
-            self._build_forward(x, training, fake_quant_bits)
+            self._build_forward(x, training, fake_quant_bits, fake_quant_range)
             self.plan_key = key
             self.bwd_key = None
         b = self.bufs
@@ -741,7 +758,14 @@ class HeadEngine(object):
                     # z -> dequantise(quantise(z)) in place; self.stats[zi] / self.ntiles[zi] are the launch's own (the conv
                     # epilogue's sums, of the unquantised values, stay in their buffer unread)
                     qparams, scratch = self.fq
-                    ops.fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch, stats=self.stats[i])
+                    if self.fq_range is None:
+                        ops.fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch, stats=self.stats[i])
+                    else:
+                        if not self.fq_range['frozen']:
+                            ops.qrange_observe(self.y[i], hc.cout, fake_quant_bits, self.fq_range['momentum'],
+                                               self.fq_range['state'], qparams, scratch)
+                        ops.fake_quantize_range(self.y[i], hc.cout, fake_quant_bits, qparams, mask=self.fq_mask,
+                                                stats=self.stats[i])
                 ops.bn_finalize(self.stats[i], self.ntiles[i], hc.cout, hc.cs_out, m, bn.weight.detach(),
                                 bn.bias.detach(), bn.running_mean, bn.running_var, bn.num_batches_tracked,
                                 BN_MOMENTUM, BN_EPS, self.scale[i], self.shift[i], self.mean[i], self.rstd[i])
@@ -749,7 +773,7 @@ class HeadEngine(object):
                         mask_out=self.out_bits)
         return self.out
 
-    def _build_forward(self, x, training, fake_quant_bits=None):
+    def _build_forward(self, x, training, fake_quant_bits=None, fake_quant_range=None):
         n, h, w, c = x.shape
         assert c == self.layers[0].cs_in
         b = self.bufs
@@ -801,6 +825,14 @@ class HeadEngine(object):
             self.fq = (b.get('fq_qparams', (4,)), b.get('fq_scratch', (ops.minmax_scratch_elems(),)))
             self.ntiles[zi] = ops.fake_quantize_tiles(self.count[zi])
             self.stats[zi] = b.get('fq_stats', (self.ntiles[zi], 2, self.layers[zi].cs_out))
+        self.fq_range = self.fq_mask = None
+        if self.fq is not None and fake_quant_range is not None:
+            # the fixed range: the clip mask of the bottleneck tensor (one byte per 4 channels of a pixel) for the backward;
+            # a frozen range's qparams are made here, once per plan, from the host pair
+            self.fq_range = dict(fake_quant_range)
+            self.fq_mask = b.get('fq_mask', ops.qrange_mask_shape(self.y[zi]), torch.uint8)
+            if self.fq_range['frozen']:
+                ops.qrange_qparams(self.fq_range['range'][0], self.fq_range['range'][1], fake_quant_bits, self.fq[0])
         self.out = b.get('out', (n, h, w, self.layers[-1].cs_out)) if self._out_buf is None else self._out_buf
         assert tuple(self.out.shape) == (n, h, w, self.layers[-1].cs_out)
         # ReLU mask of the layer output as nibbles, for the data gradient that enters this layer (MASK_BITS)
@@ -949,6 +981,8 @@ class HeadEngine(object):
                 _run(st['fused'], 'layer1.conv%d.bnbwd_transforms' % i)
             else:
                 ops.bn_bwd_apply(g, self.y[i], self.scale[i], self.shift[i], st['k123'], hc.relu, g)   # in place -> dy
+                if i == zi and getattr(self, 'fq_mask', None) is not None:
+                    ops.qrange_mask_grad(g, self.fq_mask, hc.cout)      # clipped by the fixed range: no gradient
                 if enc is not None and i == zi:          # + the gradient of the term on the bottleneck tensor
                     ops.add_inplace(g, enc[0])
             if side is not None and st['wgrad']:
@@ -1076,7 +1110,10 @@ class HeadEngine(object):
                 flops += 2 * npix * hc.cout * 4 * hc.cin
             # both consumers of dy are F(6x6,2x2) transforms: fuse the BN-backward apply into them (conv6, conv7 at full size)
             st['fused'] = None
-            if FUSE_BNBWD and wg_obj is not None and dg_obj is not None and wg_obj.tile == 6 and dg_obj.tile == 6:
+            # (not the bottleneck's conv while the fixed range is on: its dy must be materialised for qrange_mask_grad)
+            ranged = i == self.encoder_len - 1 and getattr(self, 'fq_mask', None) is not None
+            if (FUSE_BNBWD and wg_obj is not None and dg_obj is not None and wg_obj.tile == 6 and dg_obj.tile == 6
+                    and not ranged):
                 st['fused'] = ops.wino26_bnbwd_step(gbuf[i], self.y[i], self.scale[i], self.shift[i], st['k123'], hc.relu,
                                                     dg_obj, wg_obj)
                 st['wgrad'], st['dgrad'] = st['wgrad'][1:], st['dgrad'][1:]       # (their own transforms are dropped)

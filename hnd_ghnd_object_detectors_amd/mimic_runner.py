@@ -25,9 +25,11 @@ from torch import distributed as dist
 from . import configs
 from .distillation.tool import DistillationBox
 from .models import get_model, load_ckpt, save_ckpt
+from .models.ckpt import bottleneck_range_of
 from .myutils.common import file_util, yaml_util
 from .myutils.pytorch import func_util, module_util
 from .parallel import DistributedStudent
+from .structure.transformer import resolve_trained_ranges
 from .utils import data_util, main_util, misc_util
 
 _FLAGS = (  # (flag, kwargs): the reference's CLI first, this build's additions after
@@ -172,7 +174,19 @@ def distill(teacher_model, student_model, train_loader, val_loader, device, dist
     # quantisation-aware distillation (an extension): train.fake_quantize.num_bits, absent = off; refused at config time
     # for a bad width or a term on the bottleneck tensor.  Only train mode reads it: validation and the final evaluation
     # run the real codec (or none), as -transform_bottleneck decides
-    student.backbone.body.layer1.train_fake_quant_bits = configs.fake_quantize_bits_of(config)
+    layer1 = student.backbone.body.layer1
+    layer1.train_fake_quant_bits = configs.fake_quantize_bits_of(config)
+    # ... on a fixed range (train.fake_quantize.range: {type: ema}): every rank keeps its own qrange_state, like
+    # BatchNorm's batch statistics; sync_buffers() carries rank 0's copy everywhere before a validation pass, the
+    # checkpoint stores it as host floats under `bottleneck_range` (one synchronisation per saved checkpoint), and a codec
+    # with static_range 'trained' takes it
+    fq_range = configs.fake_quantize_range_of(config)
+    if fq_range is not None or getattr(layer1, 'train_fake_quant_range', None) is not None:
+        layer1.train_fake_quant_range = fq_range
+
+    def ckpt_extra(extra=None):
+        info = bottleneck_range_of(student)
+        return dict(extra or {}, **({} if info is None else {'bottleneck_range': info})) or None
     started = time.time()
     for epoch in range(args.num_epochs or train_config['num_epochs']):
         if hasattr(train_loader, 'set_epoch'):
@@ -188,17 +202,20 @@ def distill(teacher_model, student_model, train_loader, val_loader, device, dist
             student.backbone.body.layer1.use_bottleneck_transformer = use_bottleneck_transformer
             if wrapper is not None:
                 wrapper.sync_buffers()          # rank 0's BatchNorm running statistics everywhere (see parallel.py)
+            if fq_range is not None:            # the codec of this validation pass quantises on the range trained so far
+                resolve_trained_ranges(layer1.bottleneck_transformer, bottleneck_range_of(student))
             coco_evaluator = main_util.evaluate(student, val_loader, device=device)
             val_map = float(coco_evaluator.coco_eval['bbox'].stats[0])
             if val_map > best_val_map and misc_util.is_main_process():
                 print('Updating ckpt (Best BBox mAP: {:.4f} -> {:.4f})'.format(best_val_map, val_map))
                 best_val_map = val_map
-                save_ckpt(student, optimizer, lr_scheduler, best_val_map, config, args, ckpt_file_path)
+                save_ckpt(student, optimizer, lr_scheduler, best_val_map, config, args, ckpt_file_path,
+                          extra=ckpt_extra())
         elif (best_loss is None or mean_loss < best_loss) and misc_util.is_main_process():
             print('Updating ckpt (no validation set; mean distillation loss: {} -> {:.4f})'.format(best_loss, mean_loss))
             best_loss = float(mean_loss)
             save_ckpt(student, optimizer, lr_scheduler, best_val_map, config, args, ckpt_file_path,
-                      extra={'best_loss': best_loss})
+                      extra=ckpt_extra({'best_loss': best_loss}))
         lr_scheduler.step()
     if distributed:
         dist.barrier()
@@ -222,7 +239,7 @@ def main(args):
     config = yaml_util.load_yaml_file(args.config)
     if args.json is not None:
         main_util.overwrite_config(config, args.json)
-    configs.fake_quantize_bits_of(config)       # (a bad train.fake_quantize section is refused before anything is built)
+    configs.fake_quantize_range_of(config)      # (a bad train.fake_quantize section is refused before anything is built)
     distributed, _ = main_util.init_distributed_mode(args.world_size, args.dist_url)
     main_util.limit_host_threads(int(os.environ.get('LOCAL_WORLD_SIZE') or 1))
     if not torch.cuda.is_available():

@@ -41,4 +41,39 @@ def load_ckpt(ckpt_file_path, model=None, optimizer=None, lr_scheduler=None, str
         if target is not None:
             print(message)
             target.load_state_dict(ckpt[key], **kwargs)
+    if model is not None:
+        _restore_bottleneck_range(unwrap(model), ckpt, ckpt_file_path)
     return ckpt.get('best_value', 0.0), ckpt['config'], ckpt['args']
+
+
+def _layer1_of(model):
+    body = getattr(getattr(model, 'backbone', None), 'body', None)
+    return getattr(body, 'layer1', None)
+
+
+def bottleneck_range_of(model):
+    """the checkpoint entry ``bottleneck_range`` = {'min', 'max', 'steps', 'num_bits', 'momentum'} (host floats; one
+    synchronisation) of a student distilled with train.fake_quantize.range: ema, or None"""
+    layer1 = _layer1_of(unwrap(model))
+    rng = getattr(layer1, 'train_fake_quant_range', None)
+    if rng is None or layer1.train_fake_quant_bits is None:
+        return None
+    host = layer1.fake_quant_range_host()
+    return {'min': host['min'], 'max': host['max'], 'steps': host['steps'], 'num_bits': int(layer1.train_fake_quant_bits),
+            'momentum': float(rng['momentum'])}
+
+
+def _restore_bottleneck_range(model, ckpt, path):
+    """``bottleneck_range`` of the checkpoint -> the quantisers of the student's bottleneck transformer whose static_range is
+    'trained' (refused by name when the checkpoint has none), and -> qrange_state when the student has the buffer"""
+    layer1 = _layer1_of(model)
+    if layer1 is None:
+        return
+    from ..structure.transformer import resolve_trained_ranges
+    info = ckpt.get('bottleneck_range')
+    try:
+        resolve_trained_ranges(getattr(layer1, 'bottleneck_transformer', None), info)
+    except ValueError as e:
+        raise ValueError('%s (checkpoint `%s`)' % (e, path))
+    if info is not None and 'qrange_state' in getattr(layer1, '_buffers', {}):
+        layer1.qrange_state.copy_(torch.tensor([float(info['min']), float(info['max']), float(info['steps']), 0.0]))

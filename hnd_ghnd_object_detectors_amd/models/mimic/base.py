@@ -47,6 +47,9 @@ class BottleneckBase4Ext(nn.Module):
         # 1 ... 8 = in TRAIN mode the bottleneck tensor is quantised and dequantised at that width between encoder and
         # decoder, straight-through in the backward (HeadEngine.forward); None = off, the reference's training
         self.train_fake_quant_bits = None
+        # ... on a FIXED range (an extension; yaml train.fake_quantize.range: {type: ema}; include/hnd_qrange.h): see the
+        # property train_fake_quant_range.  None = the range of each batch
+        self._fq_range = None
         self.uses_ext_encoder = isinstance(encoder, ExtEncoder) and encoder.ext_classifier is not None
         from ...structure.transformer import DataLogger
         self.data_logging = isinstance(bottleneck_transformer, DataLogger)       # reference :34
@@ -60,6 +63,68 @@ class BottleneckBase4Ext(nn.Module):
         if self._engine is None:
             self._engine = E.HeadEngine(self.head_layers())
         return self._engine
+
+    @property
+    def train_fake_quant_range(self):
+        """None, or {'momentum': m, 'frozen': bool}: with train_fake_quant_bits set, the training-time fake quantiser clips
+        to a fixed range -- the exponential moving average (momentum m) of the batch min / max, kept in the buffer
+        ``qrange_state`` = {running_min, running_max, steps, 0} -- and the gradient of a clipped value is zero.  ``frozen``
+        stops the observation; the range is then whatever the buffer holds, or the literal pair of the optional key
+        ``'range': [lo, hi]``, which is written into the buffer.  Turning the mode on registers ``qrange_state`` as a
+        NON-persistent buffer (zeros), so state_dict() and the reference's checkpoint format do not change; it does not
+        exist before that."""
+        return self._fq_range
+
+    @train_fake_quant_range.setter
+    def train_fake_quant_range(self, value):
+        import math
+        import torch
+        if value is None:
+            self._fq_range = None
+            return
+        m = value.get('momentum') if isinstance(value, dict) else None
+        pair = value.get('range') if isinstance(value, dict) else None
+        if not isinstance(value, dict) or not set(value) <= {'momentum', 'frozen', 'range'} or isinstance(m, bool) or \
+                not isinstance(m, (int, float)) or not 0 < m <= 1 or not isinstance(value.get('frozen', False), bool):
+            raise ValueError('train_fake_quant_range=%r must be None or {\'momentum\': m, \'frozen\': bool} with '
+                             '0 < m <= 1' % (value,))
+        if pair is not None:
+            if not value.get('frozen', False):
+                raise ValueError('train_fake_quant_range: a literal \'range\' needs \'frozen\': True')
+            if len(pair) != 2 or not all(isinstance(v, (int, float)) and math.isfinite(v) for v in pair) or \
+                    not pair[0] < pair[1]:
+                raise ValueError('train_fake_quant_range: \'range\'=%r needs finite lo < hi' % (pair,))
+        if 'qrange_state' not in self._buffers:
+            device = next(self.parameters()).device
+            self.register_buffer('qrange_state', torch.zeros(4, dtype=torch.float32, device=device), persistent=False)
+        if pair is not None:
+            self.qrange_state.copy_(torch.tensor([float(pair[0]), float(pair[1]), 1.0, 0.0]))
+        self._fq_range = {'momentum': float(m), 'frozen': bool(value.get('frozen', False)),
+                          'range': None if pair is None else (float(pair[0]), float(pair[1]))}
+
+    def fake_quant_range_host(self):
+        """{'min', 'max', 'steps'} of qrange_state as host floats (ONE synchronisation), or None while the mode is off"""
+        if 'qrange_state' not in self._buffers:
+            return None
+        lo, hi, steps, _ = self.qrange_state.detach().cpu().tolist()
+        return {'min': lo, 'max': hi, 'steps': steps}
+
+    def _fake_quant_range_arg(self):
+        """what HeadEngine.forward takes as fake_quant_range.  A frozen range is handed over as a host pair (the engine's
+        plan makes its qparams once): the literal one, or the buffer's, read when the plan's key changes"""
+        r = self._fq_range
+        if r is None or self.train_fake_quant_bits is None:
+            return None
+        pair = r['range']
+        if r['frozen'] and pair is None:
+            pair = r.get('host_pair')
+        if r['frozen'] and pair is None:            # (once per setting of the attribute: one synchronisation)
+            host = self.fake_quant_range_host()
+            if not host['steps'] > 0 or not host['min'] < host['max']:
+                raise RuntimeError('train_fake_quant_range is frozen but qrange_state holds no range yet '
+                                   '(running_min %r, running_max %r, steps %r)' % (host['min'], host['max'], host['steps']))
+            pair = r['host_pair'] = (host['min'], host['max'])
+        return {'state': self.qrange_state, 'momentum': r['momentum'], 'frozen': r['frozen'], 'range': pair}
 
     def fake_quant_bits_checked(self):
         """train_fake_quant_bits, or the refusals that go with it (by name, before any launch of this layer): a width
@@ -94,7 +159,9 @@ class BottleneckBase4Ext(nn.Module):
         eng = self.head_engine()
         out = eng.forward(to_nhwc(x), self.training,
                           codec=self.bottleneck_transformer if use_codec else None,   # base.py:54-57
-                          fake_quant_bits=fq_bits)
+                          fake_quant_bits=fq_bits,
+                          **({} if fq_bits is None or self._fq_range is None
+                             else {'fake_quant_range': self._fake_quant_range_arg()}))
         body = self.__dict__.get('_body')
         z = None
         if self.encoder._forward_hooks or self.decoder._forward_hooks:

@@ -90,8 +90,19 @@ class _ShapeOnly(object):
 def split_rcnn_model(model, quantization, packed=False):
     """reference :215-221; ``quantization``: None, 1 ... 8 or 16 (bits of the bottleneck codec).  ``packed`` (1 ... 8 bits):
     the head emits the bit-packed link payload (structure.transformer.PackedBottleneck) and the tail unpacks it."""
+    return split_rcnn_model_ranged(model, quantization, None, packed=packed)
+
+
+def split_rcnn_model_ranged(model, quantization, static_range, packed=False):
+    """split_rcnn_model whose head quantises on a FIXED range, in one launch (include/hnd_qrange.h): ``static_range`` is
+    [lo, hi], 'trained' (resolved by load_ckpt(path, model=...) on a component of the student's bottleneck transformer, or
+    by ``head.transformer.transforms[0].resolve_trained_range(ckpt['bottleneck_range'])``) or None (= split_rcnn_model,
+    whose signature is the reference's plus ``packed`` and stays as it is)."""
     if quantization is None and packed:
         raise ValueError('split_rcnn_model(packed=True) needs a quantization width (1 ... 8)')
-    encoder_transformer = None if quantization is None else Compose([Quantizer(num_bits=quantization, packed=packed)])
+    if quantization is None and static_range is not None:
+        raise ValueError('split_rcnn_model_ranged(static_range=%r) needs a quantization width (1 ... 8)' % (static_range,))
+    encoder_transformer = None if quantization is None else \
+        Compose([Quantizer(num_bits=quantization, packed=packed, static_range=static_range)])
     decoder_transformer = None if quantization is None else Compose([Dequantizer(num_bits=quantization)])
     return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)

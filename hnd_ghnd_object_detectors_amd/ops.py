@@ -793,6 +793,132 @@ def fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None):
     return out
 
 
+# include/hnd_qrange.h: the fixed (EMA-calibrated) quantisation range.  qparams is device float[4] = {lo, hi, scale, zero_point}
+def qrange_abi():
+    return int(_L.hnd_qrange_abi())
+
+
+def _qrange_bits(who, bits):
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
+        raise ValueError('%s: bits=%r outside 1 ... 8' % (who, bits))
+    return bits
+
+
+def _qrange_geometry(who, x, c):
+    """(npix, cs) of the NHWC fp32 buffer x with c real channels"""
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() >= 1 and x.is_contiguous()):
+        raise ValueError('%s: needs a contiguous fp32 NHWC buffer' % who)
+    cs = x.shape[-1]
+    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cs or cs % 4 or x.numel() == 0:
+        raise ValueError('%s: c=%r real channels in a pixel stride of %d floats (0 < c <= stride, stride %% 4 == 0)'
+                         % (who, c, cs))
+    return x.numel() // cs, cs
+
+
+def _qrange_qparams(who, qparams):
+    if not (isinstance(qparams, torch.Tensor) and qparams.dtype == torch.float32 and qparams.numel() >= 4
+            and qparams.is_contiguous()):
+        raise ValueError('%s: qparams must be a contiguous fp32 tensor of 4 values' % who)
+    return qparams
+
+
+def qrange_observe(x, c, bits, momentum, state, qparams, scratch):
+    """fold the batch min / max of the c real channels of x into state = {running_min, running_max, steps, 0} (the first
+    call initialises, then running += momentum * (batch - running)) and write qparams of the running pair at `bits` bits"""
+    who = 'qrange_observe'
+    _qrange_bits(who, bits)
+    npix, cs = _qrange_geometry(who, x, c)
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0 < momentum <= 1:
+        raise ValueError('%s: momentum=%r outside (0, 1]' % (who, momentum))
+    _qrange_qparams(who, qparams)
+    if not (state.dtype == torch.float32 and state.numel() == 4 and state.is_contiguous()):
+        raise ValueError('%s: state must be a contiguous fp32 tensor of 4 values' % who)
+    if not (scratch.dtype == torch.float32 and scratch.numel() >= minmax_scratch_elems()):
+        raise ValueError('%s: scratch must hold minmax_scratch_elems() floats' % who)
+    check(_L.hnd_qrange_observe(ptr(x), npix, c, cs, float(momentum), bits, ptr(state), ptr(qparams), ptr(scratch),
+                                stream_ptr()), 'hnd_qrange_observe')
+
+
+def qrange_qparams(lo, hi, bits, qparams):
+    """qparams of the literal range [lo, hi] at `bits` bits, computed on the device with the codec's formula"""
+    who = 'qrange_qparams'
+    _qrange_bits(who, bits)
+    try:
+        lo, hi = float(lo), float(hi)
+    except (TypeError, ValueError):
+        raise ValueError('%s: the range (%r, %r) is not a pair of numbers' % (who, lo, hi))
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
+        raise ValueError('%s: the range needs finite lo < hi, got (%r, %r)' % (who, lo, hi))
+    _qrange_qparams(who, qparams)
+    check(_L.hnd_qrange_qparams(lo, hi, bits, ptr(qparams), stream_ptr()), 'hnd_qrange_qparams')
+    return qparams
+
+
+def qrange_mask_shape(x):
+    """shape of the clip mask of the NHWC buffer x: one byte per 4 channels of a pixel"""
+    return tuple(x.shape[:-1]) + (x.shape[-1] // 4,)
+
+
+def fake_quantize_range(x, c, bits, qparams, out=None, mask=None, stats=None):
+    """fake_quantize_bits on the FIXED range of `qparams` (read, not written), one launch: values outside the range take the
+    end codes; `mask` (uint8, qrange_mask_shape(x)) receives bit k of byte g = channel 4 g + k was not clipped.  Returns
+    the destination."""
+    who = 'fake_quantize_range'
+    _qrange_bits(who, bits)
+    npix, cs = _qrange_geometry(who, x, c)
+    _qrange_qparams(who, qparams)
+    out = x if out is None else out
+    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(x.shape)):
+        raise ValueError('%s: out must be a contiguous fp32 buffer of x\'s shape' % who)
+    if mask is not None and not (mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == npix * (cs // 4)):
+        raise ValueError('%s: mask must be a contiguous uint8 buffer of %d bytes' % (who, npix * (cs // 4)))
+    if stats is not None and not (stats.dtype == torch.float32 and stats.is_contiguous()
+                                  and stats.numel() == fake_quantize_tiles(npix) * 2 * cs):
+        raise ValueError('%s: stats must be a contiguous fp32 buffer [%d, 2, %d]' % (who, fake_quantize_tiles(npix), cs))
+    check(_L.hnd_fake_quantize_range(ptr(x), ptr(out), npix, c, cs, bits, ptr(qparams), ptr(mask), ptr(stats),
+                                     stream_ptr()), 'hnd_fake_quantize_range')
+    return out
+
+
+def qrange_mask_grad(g, mask, c):
+    """in place: +0 into the real channels of g whose mask bit is 0 (the backward of fake_quantize_range's clipping)"""
+    who = 'qrange_mask_grad'
+    npix, cs = _qrange_geometry(who, g, c)
+    if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8 and mask.is_contiguous()
+            and mask.numel() == npix * (cs // 4)):
+        raise ValueError('%s: mask must be a contiguous uint8 buffer of %d bytes' % (who, npix * (cs // 4)))
+    check(_L.hnd_qrange_mask_grad(ptr(g), ptr(mask), npix, c, cs, stream_ptr()), 'hnd_qrange_mask_grad')
+    return g
+
+
+def quantize_range_bits(x, c, bits, q, qparams):
+    """quantize_bits on the fixed range of `qparams` (read, not written): one launch"""
+    who = 'quantize_range_bits'
+    _qrange_bits(who, bits)
+    npix, cs = _qrange_geometry(who, x, c)
+    _qrange_qparams(who, qparams)
+    if not (q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
+        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
+    check(_L.hnd_quantize_range_bits(ptr(x), npix, c, cs, bits, ptr(q), ptr(qparams), stream_ptr()),
+          'hnd_quantize_range_bits')
+
+
+def quantize_pack_range_bits(x, c, bits, payload, qparams):
+    """quantize_pack_bits on the fixed range of `qparams` (read, not written): one launch"""
+    who = 'quantize_pack_range_bits'
+    _qrange_bits(who, bits)
+    _qrange_geometry(who, x, c)
+    _qrange_qparams(who, qparams)
+    if x.dim() != 4:
+        raise ValueError('%s: x must be [N, H, W, cs]' % who)
+    n, h, w, cs = x.shape
+    if not (payload.dtype == torch.uint8 and payload.is_contiguous()
+            and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0):
+        raise ValueError('%s: payload must be %d uint8 bytes' % (who, codec_packed_bytes(n * c * h * w, bits)))
+    check(_L.hnd_quantize_pack_range_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload), ptr(qparams), stream_ptr()),
+          'hnd_quantize_pack_range_bits')
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

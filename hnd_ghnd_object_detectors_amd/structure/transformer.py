@@ -16,6 +16,7 @@ Input pipeline (reference :32-55): ``ToTensor`` keeps the d
 (tiny) targets and marks the image; the /255, the flip and the model's normalise/resize/pad then run as ONE HIP
 kernel inside ``CustomRCNNTransform`` (hnd_transform_image_u8): 4x fewer host->device bytes, no host float work.
 """
+import math
 import os
 import random
 
@@ -262,17 +263,91 @@ def _check_bits(who, num_bits, packed=False):
             ' and packs 1 ... 8 bits only (16 is a half round trip, nothing to pack)' if packed else ''))
 
 
-class Quantizer(object):
+class _StaticRange(object):
+    """``static_range`` of Quantizer / FakeQuantizer (include/hnd_qrange.h): None (min / max of the tensor in front of the
+    call, three launches), a pair ``[lo, hi]`` (a fixed range: hnd_qrange_qparams runs once per pair and device, and every
+    call is then ONE launch), or ``'trained'``: the pair comes from the range a student was distilled with -- resolved by
+    ``models.load_ckpt(path, model=student)`` from the checkpoint's ``bottleneck_range`` or by ``mimic_runner.distill``
+    from the live state; calling the quantiser before that raises."""
+
+    def _init_static_range(self, static_range):
+        who = type(self).__name__
+        self._static, self._trained, self._static_qparams = None, False, {}
+        if static_range is None:
+            return
+        if self.num_bits == 16:
+            raise ValueError('%s(num_bits=16, static_range=%r): a fixed range needs a width of 1 ... 8 bits (16 is a half '
+                             'round trip, no range)' % (who, static_range))
+        if isinstance(static_range, str):
+            if static_range != 'trained':
+                raise ValueError('%s: static_range=%r must be [lo, hi] or \'trained\'' % (who, static_range))
+            self._trained = True
+            return
+        if not isinstance(static_range, (list, tuple)) or len(static_range) != 2:
+            raise ValueError('%s: static_range=%r must be [lo, hi] or \'trained\'' % (who, static_range))
+        self.set_static_range(*static_range)
+
+    @property
+    def static_range(self):
+        """None, the pair (lo, hi) in use, or 'trained' while that is unresolved"""
+        return self._static if self._static is not None else ('trained' if self._trained else None)
+
+    def set_static_range(self, lo, hi):
+        who = type(self).__name__
+        if self.num_bits == 16:
+            raise ValueError('%s(num_bits=16).set_static_range: a fixed range needs a width of 1 ... 8 bits' % who)
+        ok = all(isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v) for v in (lo, hi))
+        if not ok or not float(lo) < float(hi):
+            raise ValueError('%s: static_range needs finite lo < hi, got [%r, %r]' % (who, lo, hi))
+        self._static, self._static_qparams = (float(lo), float(hi)), {}
+
+    def resolve_trained_range(self, info):
+        """info: the ``bottleneck_range`` dict of a checkpoint ({'min', 'max', 'steps', 'num_bits', 'momentum'}); a no-op
+        unless static_range is 'trained'"""
+        who = type(self).__name__
+        if not self._trained:
+            return False
+        if not isinstance(info, dict) or not all(k in info for k in ('min', 'max', 'num_bits')):
+            raise ValueError('%s(static_range=\'trained\'): no bottleneck_range to resolve it from (the student was not '
+                             'distilled with train.fake_quantize.range: ema)' % who)
+        if int(info['num_bits']) != self.num_bits:
+            raise ValueError('%s(num_bits=%d, static_range=\'trained\'): the range was trained at %d bits'
+                             % (who, self.num_bits, int(info['num_bits'])))
+        if info.get('steps', 1) <= 0:
+            raise ValueError('%s(static_range=\'trained\'): the trained range has observed no batch yet' % who)
+        self.set_static_range(float(info['min']), float(info['max']))
+        return True
+
+    def _check_resolved(self):
+        if self._static is None and self._trained:
+            raise RuntimeError('%s(static_range=\'trained\') was called before its range was resolved: load the student '
+                               'with load_ckpt(path, model=student) or run it under distill()' % type(self).__name__)
+
+    def _static_qparams_on(self, device):
+        """None when no static range is configured; else the device qparams of the pair (one launch per pair and device)"""
+        self._check_resolved()
+        if self._static is None:
+            return None
+        if device not in self._static_qparams:
+            qp = torch.empty(4, dtype=torch.float32, device=device)
+            ops.qrange_qparams(self._static[0], self._static[1], self.num_bits, qp)
+            self._static_qparams[device] = qp
+        return self._static_qparams[device]
+
+
+class Quantizer(_StaticRange):
     """reference :131-140 at any width the reference's uint8 tensor can hold: 1 ... 8 bits (qmax = 2^num_bits - 1), or
     16 (half round trip).  ``packed=True`` returns the bit-packed link payload (PackedBottleneck) instead of the
-    one-value-per-byte QuantizedTensor."""
+    one-value-per-byte QuantizedTensor.  ``static_range``: see _StaticRange (an extension)."""
 
-    def __init__(self, num_bits=8, packed=False):
+    def __init__(self, num_bits=8, packed=False, static_range=None):
         _check_bits('Quantizer', num_bits, packed)
         self.num_bits, self.packed = num_bits, bool(packed)
         self._bufs = {}
+        self._init_static_range(static_range)
 
     def __call__(self, z, target):
+        self._check_resolved()
         buf = to_nhwc(z)                    # [N, H, W, cs] fp32 bottleneck (pad channels are 0)
         c = z.shape[1]
         if self.num_bits == 16:             # z.half(): stored back as the fp32 value of the half
@@ -286,6 +361,14 @@ class Quantizer(object):
                                torch.empty(4, dtype=torch.float32, device=buf.device),
                                torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         q, qparams, scratch = self._bufs[key]
+        fixed = self._static_qparams_on(buf.device)
+        if fixed is not None:               # one launch on the fixed range (include/hnd_qrange.h)
+            if self.packed:
+                ops.quantize_pack_range_bits(buf, c, self.num_bits, q, fixed)
+                return PackedBottleneck(q, z.shape, self.num_bits, fixed, origin=buf), target
+            ops.quantize_range_bits(buf, c, self.num_bits, q, fixed)
+            qt = q[..., :c].permute(0, 3, 1, 2)
+            return QuantizedTensor(attach(qt, q), fixed[2], fixed[3], fixed, origin=buf, channels=c), target
         if self.packed:
             ops.quantize_pack_bits(buf, c, self.num_bits, q, qparams, scratch)
             return PackedBottleneck(q, z.shape, self.num_bits, qparams, origin=buf), target
@@ -335,18 +418,28 @@ def check_fake_quant_bits(who, num_bits):
     return num_bits
 
 
-class FakeQuantizer(object):
+class FakeQuantizer(_StaticRange):
     """``[Quantizer(num_bits), Dequantizer(num_bits)]`` as ONE codec call (include/hnd_qat.h): z -> the dequantised tensor,
     bit for bit what the pair returns, written back into z's buffer.  1 ... 8 bits; an extension (the reference has no
-    such class).  ``qparams`` holds {min, max, scale, zero_point} of the newest call, on the device."""
+    such class).  ``qparams`` holds {min, max, scale, zero_point} of the newest call, on the device.  ``static_range``: see
+    _StaticRange; the call is then hnd_fake_quantize_range alone."""
 
-    def __init__(self, num_bits=8):
+    def __init__(self, num_bits=8, static_range=None):
         self.num_bits = check_fake_quant_bits('FakeQuantizer', num_bits)
         self._bufs = {}
         self.qparams = None
+        self._init_static_range(static_range)
 
     def __call__(self, z, target):
+        self._check_resolved()
         buf = to_nhwc(z)                    # [N, H, W, cs] fp32 bottleneck (pad channels are 0)
+        fixed = self._static_qparams_on(buf.device)
+        if fixed is not None:
+            self.qparams = fixed
+            ops.fake_quantize_range(buf, z.shape[1], self.num_bits, fixed)
+            if getattr(z, '_hnd', None) is buf:
+                return z, target
+            return attach(buf[..., :z.shape[1]].permute(0, 3, 1, 2), buf), target
         if buf.device not in self._bufs:
             self._bufs[buf.device] = (torch.empty(4, dtype=torch.float32, device=buf.device),
                                       torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
@@ -356,6 +449,15 @@ class FakeQuantizer(object):
         if getattr(z, '_hnd', None) is buf:         # a HIP-path tensor: a view of the buffer just rewritten
             return z, target
         return attach(buf[..., :c].permute(0, 3, 1, 2), buf), target
+
+
+def resolve_trained_ranges(transformer, info):
+    """hand ``info`` (a checkpoint's ``bottleneck_range``, or the live range of a student under distillation) to every
+    component of ``transformer`` (a Compose, a single component or None) whose static_range is 'trained'; returns how many
+    took it.  info None: refused by name if any component waits for one."""
+    parts = getattr(transformer, 'transforms', None)
+    parts = ([] if transformer is None else [transformer]) if parts is None else list(parts)
+    return sum(1 for t in parts if isinstance(t, _StaticRange) and t.resolve_trained_range(info))
 
 
 TRANSFORMER_CLASS_DICT = {'jpeg_compressor': JpegCompressor, 'jpeg_decompressor': JpegDecompressor,
