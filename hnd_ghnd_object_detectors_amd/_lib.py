@@ -1,7 +1,7 @@
 """ctypes binding of libhnd_hip.so, derived from its C headers: include/hnd_hip.h, hnd_optim.h (the further optimizer
 kinds), hnd_codec.h (the 1 ... 8-bit bottleneck codec) and hnd_qat.h (the fake-quantised bottleneck of the training step),
-each with a version of its own, and -- beside those four -- hnd_qrange.h (the fixed quantisation range of the bottleneck),
-with a version of its own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
+each with a version of its own, and -- beside those four -- hnd_qrange.h (the fixed quantisation range of the bottleneck)
+and hnd_entropy.h (the entropy-coded link payload), with versions of their own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
 dictionaries, the ABI numbers, the symbol tuples and every restype / argtypes below come from what it read, so the headers
 are the only place the contract is written down.
 
@@ -150,6 +150,13 @@ QRANGE_ABI, QRANGE_SYMBOLS = QRANGE_HEADER.defines['HND_QRANGE_ABI'], tuple(sort
 if QRANGE_HEADER.structs or QRANGE_HEADER.enums:
     raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % QRANGE_HEADER_NAME)
 
+# the entropy-coded link payload: a sixth header, read as hnd_qrange.h is
+ENTROPY_HEADER_NAME = 'hnd_entropy.h'
+ENTROPY_HEADER = _read(ENTROPY_HEADER_NAME)
+ENTROPY_ABI, ENTROPY_SYMBOLS = ENTROPY_HEADER.defines['HND_ENTROPY_ABI'], tuple(sorted(ENTROPY_HEADER.functions))
+if ENTROPY_HEADER.structs or ENTROPY_HEADER.enums:
+    raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % ENTROPY_HEADER_NAME)
+
 _lib = None
 
 
@@ -168,7 +175,7 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for header in list(HEADERS.values()) + [QRANGE_HEADER]:
+    for header in list(HEADERS.values()) + [QRANGE_HEADER, ENTROPY_HEADER]:
         for name, (res, args) in header.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -186,6 +193,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so fake-quantisation ABI %d != expected %d' % (lib.hnd_qat_abi(), QAT_ABI))
     if lib.hnd_qrange_abi() != QRANGE_ABI:
         raise HndLibraryError('libhnd_hip.so quantisation-range ABI %d != expected %d' % (lib.hnd_qrange_abi(), QRANGE_ABI))
+    if lib.hnd_entropy_abi() != ENTROPY_ABI:
+        raise HndLibraryError('libhnd_hip.so entropy-coding ABI %d != expected %d' % (lib.hnd_entropy_abi(), ENTROPY_ABI))
     _lib = lib
     return lib
 

@@ -1,0 +1,387 @@
+// include/hnd_entropy.h: the entropy-coded link payload of the bottleneck codec -- a canonical, length-limited Huffman code
+// over the quantiser's codes in independently decodable chunks of 256 symbols.  The format is the header's; this file is
+// the histogram, the three launches of the encoder and the one launch of the decoder.  Byte work and, in the decoder, the
+// fp32 sequence of unpack_dequantize_kernel (csrc/elementwise.hip): the file is built without FMA contraction.
+#include "common.h"
+#include "hnd_entropy.h"
+
+namespace {
+
+constexpr int kChunk = 256;            // symbols per chunk
+constexpr int kMaxLen = 12;            // longest code
+constexpr int kChunkBytes = kChunk * kMaxLen / 8;      // 384: capacity of one chunk
+constexpr long long kMaxNumel = 1ll << 30;
+constexpr int kLut = 1 << kMaxLen;     // the decoder's table: the next 12 stream bits -> symbol | length << 8
+
+// tables made on the host from the caller's code lengths; they reach the kernels by value
+struct EncTable {
+  uint16_t rev[256];                   // the code, bit-reversed in its length: the stream takes it least significant bit first
+  uint8_t len[256];
+};
+struct DecTable {
+  uint8_t sorted[256];                 // the symbols with a non-zero length, sorted by (length, symbol)
+  uint16_t first[kMaxLen + 1];         // the code of the first symbol of every length
+  uint16_t count[kMaxLen + 1];         // how many symbols have that length
+  uint16_t base[kMaxLen + 1];          // where they begin in `sorted`
+};
+
+// ---- host: the table of the header, checked and turned into the two by-value forms
+const char* canonical_tables(const uint8_t* lengths, int bits, EncTable* enc, DecTable* dec) {
+  const int nsym = 1 << bits;
+  unsigned kraft = 0;                  // in units of 2^-12
+  int used = 0;
+  DecTable d;
+  memset(&d, 0, sizeof(d));
+  for (int s = 0; s < nsym; ++s) {
+    const int l = lengths[s];
+    if (l > kMaxLen) return "a code length above 12";
+    if (l) {
+      kraft += 1u << (kMaxLen - l);
+      ++used;
+      ++d.count[l];
+    }
+  }
+  if (!used) return "no non-zero code length";
+  if (kraft > (1u << kMaxLen)) return "a Kraft sum above 1";
+  unsigned code = 0, at = 0, next[kMaxLen + 1], slot[kMaxLen + 1];
+  for (int l = 1; l <= kMaxLen; ++l) {
+    d.first[l] = (uint16_t)code;
+    d.base[l] = (uint16_t)at;
+    next[l] = code;
+    slot[l] = at;
+    code = (code + d.count[l]) << 1;
+    at += d.count[l];
+  }
+  if (enc) memset(enc, 0, sizeof(*enc));
+  for (int s = 0; s < nsym; ++s) {
+    const int l = lengths[s];
+    if (!l) continue;
+    const unsigned v = next[l]++;
+    d.sorted[slot[l]++] = (uint8_t)s;
+    if (enc) {
+      unsigned r = 0;
+      for (int b = 0; b < l; ++b) r |= ((v >> b) & 1u) << (l - 1 - b);
+      enc->rev[s] = (uint16_t)r;
+      enc->len[s] = (uint8_t)l;
+    }
+  }
+  if (dec) *dec = d;
+  return nullptr;
+}
+
+// ---- device
+// the (at most four) symbols i0 ... i0 + 3 of the logical NCHW order, gathered from the NHWC bytes; returns how many exist
+__device__ __forceinline__ int gather4(const uint8_t* __restrict__ q, unsigned i0, unsigned numel, unsigned hw, int c,
+                                       int cs, unsigned sym[4]) {
+  if (i0 >= numel) return 0;
+  const int count = numel - i0 < 4u ? (int)(numel - i0) : 4;
+  unsigned plane = i0 / hw, pix = i0 - plane * hw;                 // plane = img * c + ch
+  unsigned img = plane / (unsigned)c;
+  int ch = (int)(plane - img * (unsigned)c);
+  for (int k = 0; k < count; ++k) {
+    sym[k] = q[((unsigned long long)img * hw + pix) * cs + ch];
+    if (++pix == hw) {
+      pix = 0;
+      if (++ch == c) { ch = 0; ++img; }
+    }
+  }
+  return count;
+}
+
+// 16 bytes of q per thread and step; each wave of the workgroup counts into an LDS histogram of its own
+__global__ void __launch_bounds__(256) code_histogram_kernel(const uint8_t* __restrict__ q, unsigned long long total, int c,
+                                                             int cs, unsigned nsym, unsigned* __restrict__ hist) {
+  __shared__ unsigned cnt[4][256];
+  for (int i = threadIdx.x; i < 4 * 256; i += 256) (&cnt[0][0])[i] = 0;
+  __syncthreads();
+  unsigned* mine = cnt[threadIdx.x >> 6];
+  const unsigned long long nvec = total >> 4;
+  for (unsigned long long v = blockIdx.x * 256ull + threadIdx.x; v < nvec; v += (unsigned long long)gridDim.x * 256ull) {
+    const uint4 w = reinterpret_cast<const uint4*>(q)[v];
+    const unsigned words[4] = {w.x, w.y, w.z, w.w};
+    int ch = (int)((v << 4) % (unsigned)cs);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const unsigned code = (words[j >> 2] >> (8 * (j & 3))) & 255u;
+      if (ch < c && code < nsym) atomicAdd(&mine[code], 1u);
+      if (++ch == cs) ch = 0;
+    }
+  }
+  if (blockIdx.x == 0) {                                            // the bytes after the last whole 16 (fewer than 16)
+    const unsigned long long e = (nvec << 4) + threadIdx.x;
+    if (threadIdx.x < 16 && e < total) {
+      const unsigned code = q[e];
+      if ((int)(e % (unsigned)cs) < c && code < nsym) atomicAdd(&mine[code], 1u);
+    }
+  }
+  __syncthreads();
+  const unsigned sum = cnt[0][threadIdx.x] + cnt[1][threadIdx.x] + cnt[2][threadIdx.x] + cnt[3][threadIdx.x];
+  if (sum) atomicAdd(&hist[threadIdx.x], sum);
+}
+
+// launch 1 of the encoder: one wave per chunk, the chunk's byte count
+__global__ void __launch_bounds__(256) chunk_bytes_kernel(const uint8_t* __restrict__ q, unsigned numel, unsigned hw, int c,
+                                                          int cs, const EncTable tab, unsigned nchunks,
+                                                          unsigned* __restrict__ sizes) {
+  __shared__ uint8_t len[256];
+  len[threadIdx.x] = tab.len[threadIdx.x];
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (unsigned chunk = blockIdx.x * 4u + (threadIdx.x >> 6); chunk < nchunks; chunk += gridDim.x * 4u) {
+    unsigned sym[4], nb = 0;
+    const int count = gather4(q, chunk * (unsigned)kChunk + lane * 4u, numel, hw, c, cs, sym);
+    for (int k = 0; k < count; ++k) nb += len[sym[k]];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) nb += __shfl_xor(nb, o);
+    if (lane == 0) sizes[chunk] = (nb + 7u) >> 3;
+  }
+}
+
+// launch 2: offsets = exclusive prefix sum of sizes, offsets[n] = the total.  ONE workgroup walks the array in tiles of 1024
+// with a running carry: nothing waits on another workgroup.
+__global__ void __launch_bounds__(1024) chunk_offsets_kernel(const unsigned* __restrict__ sizes, unsigned n,
+                                                             unsigned* __restrict__ offsets) {
+  __shared__ unsigned wsum[16];
+  __shared__ unsigned carry_s;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (threadIdx.x == 0) carry_s = 0;
+  __syncthreads();
+  for (unsigned t0 = 0; t0 < n; t0 += 1024u) {
+    const unsigned i = t0 + threadIdx.x;
+    const unsigned v = i < n ? sizes[i] : 0u;
+    unsigned incl = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_up(incl, o);
+      if (lane >= o) incl += up;
+    }
+    if (lane == 63) wsum[wave] = incl;
+    __syncthreads();
+    unsigned before = carry_s;
+    for (int k = 0; k < wave; ++k) before += wsum[k];
+    if (i < n) offsets[i] = before + incl - v;
+    __syncthreads();
+    if (threadIdx.x == 1023) carry_s = before + incl;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) offsets[n] = carry_s;
+}
+
+// launch 3: one wave per chunk.  A lane's four codes make one word of at most 48 bits; the lanes' bit counts meet in a wave
+// prefix scan; the words are OR-ed into the wave's LDS staging buffer (zeroed first: the pad bits of the last byte stay 0)
+// and the chunk's bytes leave lane by lane, byte i of the chunk from lane i % 64.
+__global__ void __launch_bounds__(256) chunk_encode_kernel(const uint8_t* __restrict__ q, unsigned numel, unsigned hw, int c,
+                                                           int cs, const EncTable tab, unsigned nchunks,
+                                                           const unsigned* __restrict__ offsets,
+                                                           uint8_t* __restrict__ payload) {
+  constexpr int kStage = kChunkBytes / 4 + 4;                       // 96 dwords and room for the shifted top of the last word
+  __shared__ unsigned code[256];                                    // rev | len << 16
+  __shared__ unsigned stage[4][kStage];
+  code[threadIdx.x] = (unsigned)tab.rev[threadIdx.x] | ((unsigned)tab.len[threadIdx.x] << 16);
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned* st = stage[wave];
+  for (unsigned chunk = blockIdx.x * 4u + wave; chunk < nchunks; chunk += gridDim.x * 4u) {
+    for (int i = lane; i < kStage; i += 64) st[i] = 0;
+    unsigned sym[4], nb = 0;
+    unsigned long long word = 0;
+    const int count = gather4(q, chunk * (unsigned)kChunk + lane * 4u, numel, hw, c, cs, sym);
+    for (int k = 0; k < count; ++k) {
+      const unsigned e = code[sym[k]];
+      word |= (unsigned long long)(e & 0xFFFFu) << nb;
+      nb += e >> 16;
+    }
+    unsigned incl = nb;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const unsigned up = __shfl_up(incl, o);
+      if (lane >= o) incl += up;
+    }
+    const unsigned pos = incl - nb, nbytes = (__shfl(incl, 63) + 7u) >> 3;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // the zeros before the ORs (one wave: program order in LDS)
+    if (nb) {
+      const unsigned d = pos >> 5, sh = pos & 31u;
+      const unsigned long long lo = word << sh;
+      const unsigned hi = sh ? (unsigned)(word >> (64u - sh)) : 0u;
+      if ((unsigned)lo) atomicOr(&st[d], (unsigned)lo);
+      if ((unsigned)(lo >> 32)) atomicOr(&st[d + 1], (unsigned)(lo >> 32));
+      if (hi) atomicOr(&st[d + 2], hi);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    uint8_t* dst = payload + offsets[chunk];
+    for (unsigned i = lane; i < nbytes; i += 64) dst[i] = (uint8_t)(st[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+// dword `dw` of the payload; a byte at or beyond nbytes reads as 0 and is not touched
+__device__ __forceinline__ unsigned payload_dword(const uint8_t* __restrict__ p, unsigned dw, unsigned nbytes) {
+  if (dw < (nbytes >> 2)) return reinterpret_cast<const unsigned*>(p)[dw];
+  unsigned v = 0;
+  if (dw == (nbytes >> 2))
+    for (unsigned b = 0; b < (nbytes & 3u); ++b) v |= (unsigned)p[dw * 4u + b] << (8 * b);
+  return v;
+}
+
+constexpr int kTilePix = 2048;                         // pixels of one image per workgroup
+constexpr int kTileChunks = kTilePix / kChunk + 1;     // 9: chunks one channel's 2048 symbols can overlap
+constexpr int kGroup = 16;                             // channels decoded and stored together
+constexpr int kSlotDwords = kChunk / 4 + 1;            // 65: a chunk's symbols, one byte each, and a dword of bank padding
+
+__global__ void __launch_bounds__(256) decode_dequantize_kernel(const uint8_t* __restrict__ payload, unsigned payload_bytes,
+                                                                const unsigned* __restrict__ offsets, const DecTable tab,
+                                                                const float* __restrict__ qp, float* __restrict__ x,
+                                                                unsigned hw, int c, int cs, unsigned tiles) {
+#pragma clang fp contract(off)
+  __shared__ uint16_t lut[kLut];
+  __shared__ unsigned stage[kGroup * kTileChunks * kSlotDwords];
+  for (unsigned e = threadIdx.x; e < (unsigned)kLut; e += 256) {    // canonical decoding of every 12-bit window
+    unsigned entry = kMaxLen << 8, v = 0;                           // no code begins here (a table with Kraft < 1): symbol 0
+    for (int l = 1; l <= kMaxLen; ++l) {
+      v = (v << 1) | ((e >> (l - 1)) & 1u);                         // the first l stream bits, most significant code bit first
+      const unsigned d = v - tab.first[l];
+      if (v >= tab.first[l] && d < tab.count[l]) {
+        entry = (unsigned)tab.sorted[tab.base[l] + d] | ((unsigned)l << 8);
+        break;
+      }
+    }
+    lut[e] = (uint16_t)entry;
+  }
+  const unsigned img = blockIdx.x / tiles, p0 = (blockIdx.x - img * tiles) * (unsigned)kTilePix;
+  const unsigned npx = hw - p0 < (unsigned)kTilePix ? hw - p0 : (unsigned)kTilePix;
+  const float scale = qp[2], zp = qp[3];
+  for (int g0 = 0; g0 < c; g0 += kGroup) {
+    const int gc = c - g0 < kGroup ? c - g0 : kGroup;
+    __syncthreads();                                                // the table is built; the staging buffer is free again
+    if ((int)threadIdx.x < gc * kTileChunks) {
+      const int chg = threadIdx.x / kTileChunks, k = threadIdx.x - chg * kTileChunks;
+      const unsigned s0 = (img * (unsigned)c + g0 + chg) * hw + p0; // first symbol of this channel in the tile (< 2^30)
+      const unsigned chunk = (s0 >> 8) + k;
+      if (chunk <= ((s0 + npx - 1u) >> 8)) {                        // the chunk overlaps the tile, so it exists
+        const unsigned o0 = offsets[chunk];
+        unsigned dw = o0 >> 2;
+        unsigned long long buf = payload_dword(payload, dw++, payload_bytes) >> (8 * (o0 & 3u));
+        int have = 32 - 8 * (int)(o0 & 3u);
+        unsigned* slot = stage + threadIdx.x * kSlotDwords;
+        for (int j = 0; j < kChunk / 4; ++j) {                      // always 256 symbols: past a short chunk's end they are
+          unsigned packed = 0;                                      // whatever zeros decode to, and nobody reads them
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            if (have < kMaxLen) {
+              buf |= (unsigned long long)payload_dword(payload, dw++, payload_bytes) << have;
+              have += 32;
+            }
+            const unsigned e = lut[(unsigned)buf & (kLut - 1)];
+            packed |= (e & 255u) << (8 * b);
+            buf >>= e >> 8;
+            have -= (int)(e >> 8);
+          }
+          slot[j] = packed;
+        }
+      }
+    }
+    __syncthreads();
+    const int gend = g0 + kGroup >= c ? cs : g0 + kGroup;           // the last group also clears the pad channels
+    const unsigned nq = (unsigned)(gend - g0) >> 2;
+    const uint8_t* sb = reinterpret_cast<const uint8_t*>(stage);
+    for (unsigned idx = threadIdx.x; idx < npx * nq; idx += 256) {
+      const unsigned pix = idx / nq, qd = idx - pix * nq;
+      float out[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int ch = g0 + (int)qd * 4 + e;
+        out[e] = 0.f;
+        if (ch < c) {
+          const unsigned s0 = (img * (unsigned)c + ch) * hw + p0, s = s0 + pix;
+          const unsigned slot = (unsigned)(ch - g0) * kTileChunks + ((s >> 8) - (s0 >> 8));
+          out[e] = __fmul_rn(scale, __fsub_rn((float)sb[slot * (kSlotDwords * 4) + (s & 255u)], zp));   // scale * (q - zero_point)
+        }
+      }
+      float4 v4 = make_float4(out[0], out[1], out[2], out[3]);
+      *reinterpret_cast<float4*>(x + ((unsigned long long)img * hw + p0 + pix) * cs + g0 + qd * 4u) = v4;
+    }
+  }
+}
+
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15u) == 0;
+}
+
+inline bool good_geometry(int n, int h, int w, int c, int cs) {
+  return n > 0 && h > 0 && w > 0 && c > 0 && cs >= c && cs % 4 == 0 && (long long)n * c <= kMaxNumel &&
+         (long long)h * w <= kMaxNumel && (long long)n * c * ((long long)h * w) <= kMaxNumel;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hnd_entropy_abi(void) { return HND_ENTROPY_ABI; }
+
+int64_t hnd_entropy_chunks(int64_t numel) {
+  return numel <= 0 || numel > kMaxNumel ? 0 : (numel + kChunk - 1) / kChunk;
+}
+
+size_t hnd_entropy_capacity(int64_t numel) { return (size_t)hnd_entropy_chunks(numel) * kChunkBytes; }
+
+size_t hnd_entropy_scratch_bytes(int64_t numel) { return (size_t)hnd_entropy_chunks(numel) * sizeof(uint32_t); }
+
+int hnd_code_histogram(const uint8_t* q, int n, int h, int w, int c, int cs, int bits, void* hist, void* stream) {
+  HND_REQUIRE(q && hist, "hnd_code_histogram: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_code_histogram: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(good_geometry(n, h, w, c, cs),
+              "hnd_code_histogram: bad geometry (n, h, w, c > 0, cs >= c, cs %% 4 == 0, n * c * h * w <= 2^30)");
+  HND_REQUIRE(aligned16(q, hist), "hnd_code_histogram: q and hist must be 16-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  const unsigned long long total = (unsigned long long)n * h * w * cs;
+  if (hipMemsetAsync(hist, 0, 256 * sizeof(uint32_t), s) != hipSuccess) return hnd::check_launch("hnd_code_histogram");
+  unsigned long long blocks = ((total >> 4) + 255) / 256;
+  blocks = blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+  hipLaunchKernelGGL(code_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, s, q, total, c, cs, 1u << bits,
+                     (unsigned*)hist);
+  return hnd::check_launch("hnd_code_histogram");
+}
+
+int hnd_entropy_encode(const uint8_t* q, int n, int h, int w, int c, int cs, int bits, const uint8_t* lengths_host,
+                       uint8_t* payload, void* offsets, void* scratch, void* stream) {
+  HND_REQUIRE(q && lengths_host && payload && offsets && scratch, "hnd_entropy_encode: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_entropy_encode: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(good_geometry(n, h, w, c, cs),
+              "hnd_entropy_encode: bad geometry (n, h, w, c > 0, cs >= c, cs %% 4 == 0, n * c * h * w <= 2^30)");
+  HND_REQUIRE(aligned16(q, payload, offsets) && aligned16(scratch),
+              "hnd_entropy_encode: q, payload, offsets and scratch must be 16-byte aligned");
+  EncTable tab;
+  const char* bad = canonical_tables(lengths_host, bits, &tab, nullptr);
+  HND_REQUIRE(!bad, "hnd_entropy_encode: bad table of code lengths: %s", bad);
+  hipStream_t s = hnd::as_stream(stream);
+  const unsigned hw = (unsigned)h * w, numel = (unsigned)n * c * hw, nchunks = (numel + kChunk - 1) / kChunk;
+  unsigned blocks = (nchunks + 3) / 4;
+  blocks = blocks > 2048 ? 2048 : blocks;
+  hipLaunchKernelGGL(chunk_bytes_kernel, dim3(blocks), dim3(256), 0, s, q, numel, hw, c, cs, tab, nchunks, (unsigned*)scratch);
+  hipLaunchKernelGGL(chunk_offsets_kernel, dim3(1), dim3(1024), 0, s, (const unsigned*)scratch, nchunks, (unsigned*)offsets);
+  hipLaunchKernelGGL(chunk_encode_kernel, dim3(blocks), dim3(256), 0, s, q, numel, hw, c, cs, tab, nchunks,
+                     (const unsigned*)offsets, payload);
+  return hnd::check_launch("hnd_entropy_encode");
+}
+
+int hnd_entropy_decode_dequantize(const uint8_t* payload, int64_t payload_bytes, const void* offsets,
+                                  const uint8_t* lengths_host, const float* qparams, float* x, int n, int h, int w, int c,
+                                  int cs, int bits, void* stream) {
+  HND_REQUIRE(payload && offsets && lengths_host && qparams && x, "hnd_entropy_decode_dequantize: null pointer");
+  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_entropy_decode_dequantize: bits %d outside 1 ... 8", bits);
+  HND_REQUIRE(good_geometry(n, h, w, c, cs),
+              "hnd_entropy_decode_dequantize: bad geometry (n, h, w, c > 0, cs >= c, cs %% 4 == 0, n * c * h * w <= 2^30)");
+  HND_REQUIRE(payload_bytes > 0 && payload_bytes <= (int64_t)kMaxNumel / kChunk * kChunkBytes,
+              "hnd_entropy_decode_dequantize: payload_bytes %lld outside 1 ... the capacity of 2^30 values",
+              (long long)payload_bytes);
+  HND_REQUIRE(aligned16(payload, offsets, qparams) && aligned16(x),
+              "hnd_entropy_decode_dequantize: payload, offsets, qparams and x must be 16-byte aligned");
+  DecTable tab;
+  const char* bad = canonical_tables(lengths_host, bits, nullptr, &tab);
+  HND_REQUIRE(!bad, "hnd_entropy_decode_dequantize: bad table of code lengths: %s", bad);
+  const unsigned hw = (unsigned)h * w, tiles = (hw + kTilePix - 1) / kTilePix;
+  hipLaunchKernelGGL(decode_dequantize_kernel, dim3((unsigned)n * tiles), dim3(256), 0, hnd::as_stream(stream), payload,
+                     (unsigned)payload_bytes, (const unsigned*)offsets, tab, qparams, x, hw, c, cs, tiles);
+  return hnd::check_launch("hnd_entropy_decode_dequantize");
+}
+
+}  // extern "C"

@@ -106,3 +106,17 @@ def split_rcnn_model_ranged(model, quantization, static_range, packed=False):
         Compose([Quantizer(num_bits=quantization, packed=packed, static_range=static_range)])
     decoder_transformer = None if quantization is None else Compose([Dequantizer(num_bits=quantization)])
     return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)
+
+
+def split_rcnn_model_entropy(model, quantization, static_range=None, code_lengths=None):
+    """split_rcnn_model whose head emits the ENTROPY-CODED link payload (structure.transformer.EntropyBottleneck,
+    include/hnd_entropy.h) and whose tail decodes and dequantises it in one launch: the detections are those of
+    split_rcnn_model at the same width, bit for bit.  ``quantization``: 1 ... 8; ``static_range`` as in
+    split_rcnn_model_ranged; ``code_lengths``: a fixed, complete table of 2^quantization code lengths (no histogram and no
+    read-back in the head) or None (the table is built from every tensor's own histogram)."""
+    if quantization is None:
+        raise ValueError('split_rcnn_model_entropy needs a quantization width (1 ... 8)')
+    encoder_transformer = Compose([Quantizer(num_bits=quantization, static_range=static_range, entropy=True,
+                                             code_lengths=code_lengths)])
+    decoder_transformer = Compose([Dequantizer(num_bits=quantization)])
+    return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)

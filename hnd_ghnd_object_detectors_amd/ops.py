@@ -919,6 +919,94 @@ def quantize_pack_range_bits(x, c, bits, payload, qparams):
           'hnd_quantize_pack_range_bits')
 
 
+# include/hnd_entropy.h: the entropy-coded link payload (canonical Huffman code in chunks of 256 symbols).  q is the
+# one-value-per-byte uint8 NHWC tensor [N, H, W, cs] of the quantisers above with c real channels; `lengths` is a host
+# bytes object of 2^bits code lengths.
+def entropy_abi():
+    return int(_L.hnd_entropy_abi())
+
+
+def entropy_chunks(numel):
+    """chunks of 256 symbols that `numel` values make; 0 for numel <= 0 or numel > 2^30"""
+    return int(_L.hnd_entropy_chunks(int(numel)))
+
+
+def entropy_capacity(numel):
+    """bytes the payload buffer of `numel` values must have: 384 per chunk; 0 for bad arguments"""
+    return int(_L.hnd_entropy_capacity(int(numel)))
+
+
+def entropy_scratch_bytes(numel):
+    """bytes of the encoder's scratch buffer; 0 for bad arguments"""
+    return int(_L.hnd_entropy_scratch_bytes(int(numel)))
+
+
+def _entropy_geometry(who, t, c, bits, dtype):
+    _qrange_bits(who, bits)
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 4 and t.is_contiguous()):
+        raise ValueError('%s: needs a contiguous %s NHWC buffer [N, H, W, cs]' % (who, dtype))
+    n, h, w, cs = t.shape
+    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cs or cs % 4 or t.numel() == 0:
+        raise ValueError('%s: c=%r real channels in a pixel stride of %d (0 < c <= stride, stride %% 4 == 0)' % (who, c, cs))
+    if entropy_chunks(n * c * h * w) == 0:
+        raise ValueError('%s: %d values are more than the 2^30 one stream holds' % (who, n * c * h * w))
+    return n, h, w, cs
+
+
+def _entropy_lengths(who, lengths, bits):
+    if not isinstance(lengths, (bytes, bytearray)) or len(lengths) != 1 << bits:
+        raise ValueError('%s: lengths must be a bytes object of 2^%d code lengths' % (who, bits))
+    return bytes(lengths)
+
+
+def _entropy_words(who, t, name, count):
+    if not (isinstance(t, torch.Tensor) and t.dtype in (torch.int32, torch.uint8) and t.is_contiguous()
+            and t.numel() * t.element_size() == 4 * count):
+        raise ValueError('%s: %s must be a contiguous int32 buffer of %d words' % (who, name, count))
+    return t
+
+
+def code_histogram(q, c, bits, hist):
+    """hist (int32[256], zeroed and filled by the call): how often every code occurs in the c real channels of q"""
+    who = 'code_histogram'
+    n, h, w, cs = _entropy_geometry(who, q, c, bits, torch.uint8)
+    _entropy_words(who, hist, 'hist', 256)
+    check(_L.hnd_code_histogram(ptr(q), n, h, w, c, cs, bits, ptr(hist), stream_ptr()), 'hnd_code_histogram')
+    return hist
+
+
+def entropy_encode(q, c, bits, lengths, payload, offsets, scratch):
+    """offsets (int32[chunks + 1]) and the stream (payload, uint8[entropy_capacity]) of the logical NCHW codes of q under
+    the canonical code of `lengths`: three launches, no host synchronisation"""
+    who = 'entropy_encode'
+    n, h, w, cs = _entropy_geometry(who, q, c, bits, torch.uint8)
+    numel = n * c * h * w
+    lengths = _entropy_lengths(who, lengths, bits)
+    if not (payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() == entropy_capacity(numel)):
+        raise ValueError('%s: payload must be %d uint8 bytes' % (who, entropy_capacity(numel)))
+    _entropy_words(who, offsets, 'offsets', entropy_chunks(numel) + 1)
+    if not (scratch.is_contiguous() and scratch.numel() * scratch.element_size() >= entropy_scratch_bytes(numel)):
+        raise ValueError('%s: scratch must hold %d bytes' % (who, entropy_scratch_bytes(numel)))
+    check(_L.hnd_entropy_encode(ptr(q), n, h, w, c, cs, bits, lengths, ptr(payload), ptr(offsets), ptr(scratch),
+                                stream_ptr()), 'hnd_entropy_encode')
+
+
+def entropy_decode_dequantize(payload, offsets, lengths, qparams, x, c, bits):
+    """the inverse, fused with the dequantiser: scale * (q - zero_point) into the c real channels of x [N, H, W, cs], 0 into
+    its pad channels, one launch; the bits of unpack_dequantize_bits.  `payload` may be the whole capacity or its first
+    offsets[chunks] bytes."""
+    who = 'entropy_decode_dequantize'
+    n, h, w, cs = _entropy_geometry(who, x, c, bits, torch.float32)
+    lengths = _entropy_lengths(who, lengths, bits)
+    _qrange_qparams(who, qparams)
+    if not (payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() > 0):
+        raise ValueError('%s: payload must be a non-empty contiguous uint8 buffer' % who)
+    _entropy_words(who, offsets, 'offsets', entropy_chunks(n * c * h * w) + 1)
+    check(_L.hnd_entropy_decode_dequantize(ptr(payload), payload.numel(), ptr(offsets), lengths, ptr(qparams), ptr(x),
+                                           n, h, w, c, cs, bits, stream_ptr()), 'hnd_entropy_decode_dequantize')
+    return x
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

@@ -3,7 +3,8 @@
 The reference applies them ONLY at evaluation time with ``-transform_bottleneck`` (src/models/mimic/base.py:54-57;
 mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantizer`` run as fused HIP kernels
 (global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
-payload, include/hnd_codec.h; dequantise) on the NHWC bottleneck buffer; the 16-bit variants are a half round trip.
+payload, include/hnd_codec.h, or entropy-coded in chunks, include/hnd_entropy.h; dequantise) on the NHWC bottleneck buffer;
+the 16-bit variants are a half round trip.
 ``FakeQuantizer`` (an extension) is the pair as one call (include/hnd_qat.h) -- the launch the TRAINING step runs on the
 bottleneck tensor when ``train.fake_quantize`` is set (engine.HeadEngine.forward).
 ``JpegCompressor`` / ``JpegDecompressor`` (:94-128: the uint8 bottleneck image through a JPEG file)
@@ -253,6 +254,103 @@ class PackedBottleneck(object):
         return self.payload.numel()
 
 
+MAX_CODE_LEN = 12          # longest code of include/hnd_entropy.h
+
+
+def check_code_lengths(who, lengths, num_bits, complete=False):
+    """the table of include/hnd_entropy.h as bytes: 2^num_bits lengths in 0 ... 12, at least one non-zero, Kraft sum <= 1;
+    ``complete``: every length non-zero (a fixed table must be able to code any tensor).  Anything else is refused by name."""
+    try:
+        table = [int(v) for v in lengths]
+        ok = all(float(v) == int(v) and not isinstance(v, bool) for v in lengths)
+    except (TypeError, ValueError):
+        table, ok = [], False
+    if not ok or len(table) != 1 << num_bits:
+        raise ValueError('%s: code_lengths must be %d integers (one per code of %d bits)' % (who, 1 << num_bits, num_bits))
+    if any(not 0 <= v <= MAX_CODE_LEN for v in table):
+        raise ValueError('%s: code_lengths outside 0 ... %d' % (who, MAX_CODE_LEN))
+    if complete and not all(table):
+        raise ValueError('%s: a fixed table of code_lengths must be complete: every one of the %d lengths non-zero'
+                         % (who, 1 << num_bits))
+    if not any(table):
+        raise ValueError('%s: code_lengths has no non-zero length' % who)
+    if sum(1 << (MAX_CODE_LEN - v) for v in table if v) > 1 << MAX_CODE_LEN:
+        raise ValueError('%s: code_lengths has a Kraft sum above 1: no prefix code has these lengths' % who)
+    return bytes(table)
+
+
+def huffman_lengths(hist, num_bits, max_len=MAX_CODE_LEN):
+    """Code lengths (bytes, 2^num_bits of them) of an optimal prefix code of the histogram ``hist`` whose longest code is
+    ``max_len`` bits -- the ``lengths`` of include/hnd_entropy.h.  Deterministic host code.
+
+    Method: package-merge (Larmore & Hirschberg 1990).  The occurring symbols, sorted by (count, symbol), are the leaves.
+    Starting from the leaves, max_len - 1 times: pair the current list's items in order (an odd last item is dropped) and
+    merge the pairs ("packages") with the leaves, by weight, a leaf before a package of equal weight.  The first 2 m - 2
+    items of the final list are taken (m = occurring symbols) and a symbol's length is the number of taken items that contain
+    it.  The result is an optimal code under the length limit, so its Kraft sum is exactly 1 for m >= 2, its cost
+    sum(hist * len) never exceeds the flat code's num_bits * sum(hist) (the flat code is one of the candidates), and it
+    equals the unconstrained Huffman cost wherever that tree is no deeper than max_len.  Absent symbols get 0; a single
+    occurring symbol gets 1.  Should the cost ever exceed the flat code's, the flat code (num_bits for every occurring
+    symbol) is returned instead."""
+    nsym = 1 << num_bits
+    counts = [int(v) for v in hist][:nsym]
+    if len(counts) != nsym or any(v < 0 for v in counts) or any(int(v) for v in list(hist)[nsym:]):
+        raise ValueError('huffman_lengths: hist must hold a count >= 0 for each of the %d codes and 0 beyond them' % nsym)
+    if not num_bits <= max_len <= MAX_CODE_LEN:
+        raise ValueError('huffman_lengths: max_len=%r outside %d ... %d' % (max_len, num_bits, MAX_CODE_LEN))
+    leaves = sorted((counts[s], s) for s in range(nsym) if counts[s])
+    if not leaves:
+        raise ValueError('huffman_lengths: an empty histogram')
+    lengths = [0] * nsym
+    if len(leaves) == 1:
+        lengths[leaves[0][1]] = 1
+        return bytes(lengths)
+    leaf_items = [(w, (s,)) for w, s in leaves]                  # (weight, the symbols it contains, with multiplicity)
+    items = leaf_items
+    for _ in range(max_len - 1):
+        packages = [(items[i][0] + items[i + 1][0], items[i][1] + items[i + 1][1]) for i in range(0, len(items) - 1, 2)]
+        merged, a, b = [], 0, 0
+        while a < len(leaf_items) or b < len(packages):
+            if b == len(packages) or (a < len(leaf_items) and leaf_items[a][0] <= packages[b][0]):
+                merged.append(leaf_items[a])
+                a += 1
+            else:
+                merged.append(packages[b])
+                b += 1
+        items = merged
+    for _, symbols in items[:2 * len(leaves) - 2]:
+        for s in symbols:
+            lengths[s] += 1
+    if sum(c * l for c, l in zip(counts, lengths)) > num_bits * sum(counts):
+        lengths = [num_bits if c else 0 for c in counts]
+    return bytes(lengths)
+
+
+class EntropyBottleneck(object):
+    """The quantised bottleneck as an entropy-coded stream (``Quantizer(num_bits, entropy=True)``; format:
+    include/hnd_entropy.h): ``payload`` is a 1-D uint8 device tensor of the stream's CAPACITY of which the first ``nbytes``
+    are the stream, ``offsets`` an int32 device tensor of chunks + 1 byte offsets, ``lengths`` the host ``bytes`` of the
+    2^num_bits code lengths; ``scale`` / ``zero_point`` are 0-dim device views of ``qparams`` as in QuantizedTensor."""
+
+    def __init__(self, payload, offsets, lengths, shape, num_bits, qparams, origin=None):
+        self.payload, self.offsets, self.lengths = payload, offsets, bytes(lengths)
+        self.shape, self.num_bits = tuple(int(s) for s in shape), num_bits
+        self.qparams, self.scale, self.zero_point, self.origin = qparams, qparams[2], qparams[3], origin
+        self._nbytes = None
+
+    @property
+    def nbytes(self):
+        """bytes of the stream: offsets[chunks], one small device read, cached"""
+        if self._nbytes is None:
+            self._nbytes = int(self.offsets[-1].item()) & 0xFFFFFFFF
+        return self._nbytes
+
+    @property
+    def link_bytes(self):
+        """everything that crosses the link: the stream, the offsets, the table of lengths, scale and zero point"""
+        return self.nbytes + 4 * self.offsets.numel() + (1 << self.num_bits) + 8
+
+
 SUPPORTED_BITS = tuple(range(1, 9)) + (16,)
 
 
@@ -338,13 +436,45 @@ class _StaticRange(object):
 class Quantizer(_StaticRange):
     """reference :131-140 at any width the reference's uint8 tensor can hold: 1 ... 8 bits (qmax = 2^num_bits - 1), or
     16 (half round trip).  ``packed=True`` returns the bit-packed link payload (PackedBottleneck) instead of the
-    one-value-per-byte QuantizedTensor.  ``static_range``: see _StaticRange (an extension)."""
+    one-value-per-byte QuantizedTensor.  ``static_range``: see _StaticRange (an extension).  ``entropy=True`` (an extension,
+    1 ... 8 bits, not with ``packed``) runs the same quantise path and then entropy-codes its bytes (EntropyBottleneck,
+    include/hnd_entropy.h): a histogram launch, one 1 KB read-back (the table depends on the data), huffman_lengths on the
+    host and the encoder's three launches.  ``code_lengths`` (with ``entropy``) fixes the table instead -- all 2^num_bits
+    lengths non-zero -- and the call then has neither the histogram nor the read-back."""
 
-    def __init__(self, num_bits=8, packed=False, static_range=None):
+    def __init__(self, num_bits=8, packed=False, static_range=None, entropy=False, code_lengths=None):
         _check_bits('Quantizer', num_bits, packed)
-        self.num_bits, self.packed = num_bits, bool(packed)
-        self._bufs = {}
+        self.num_bits, self.packed, self.entropy = num_bits, bool(packed), bool(entropy)
+        if self.entropy and self.packed:
+            raise ValueError('Quantizer(entropy=True, packed=True): the link payload is either entropy-coded or bit-packed')
+        if self.entropy and num_bits == 16:
+            raise ValueError('Quantizer(num_bits=16, entropy=True): entropy coding needs a width of 1 ... 8 bits (16 is a '
+                             'half round trip, no codes)')
+        if code_lengths is not None and not self.entropy:
+            raise ValueError('Quantizer(code_lengths=...) needs entropy=True: the table belongs to the entropy coder')
+        self.code_lengths = None if code_lengths is None else \
+            check_code_lengths('Quantizer(entropy=True)', code_lengths, num_bits, complete=True)
+        self._bufs, self._entropy_bufs = {}, {}
         self._init_static_range(static_range)
+
+    def _entropy_code(self, q, c, qparams, shape, origin):
+        """q (uint8 NHWC, one value per byte) -> EntropyBottleneck: [histogram, one 1 KB read-back, huffman_lengths] unless
+        the table is fixed, then the three launches of the encoder (include/hnd_entropy.h)"""
+        key = (tuple(q.shape), c, q.device)
+        if key not in self._entropy_bufs:
+            numel = q.numel() // q.shape[-1] * c
+            self._entropy_bufs[key] = (
+                torch.empty(ops.entropy_capacity(numel), dtype=torch.uint8, device=q.device),
+                torch.empty(ops.entropy_chunks(numel) + 1, dtype=torch.int32, device=q.device),
+                torch.empty(ops.entropy_scratch_bytes(numel) // 4, dtype=torch.int32, device=q.device),
+                torch.empty(256, dtype=torch.int32, device=q.device))
+        payload, offsets, scratch, hist = self._entropy_bufs[key]
+        lengths = self.code_lengths
+        if lengths is None:
+            ops.code_histogram(q, c, self.num_bits, hist)
+            lengths = huffman_lengths(hist.cpu().tolist(), self.num_bits)
+        ops.entropy_encode(q, c, self.num_bits, lengths, payload, offsets, scratch)
+        return EntropyBottleneck(payload, offsets, lengths, shape, self.num_bits, qparams, origin=origin)
 
     def __call__(self, z, target):
         self._check_resolved()
@@ -367,6 +497,8 @@ class Quantizer(_StaticRange):
                 ops.quantize_pack_range_bits(buf, c, self.num_bits, q, fixed)
                 return PackedBottleneck(q, z.shape, self.num_bits, fixed, origin=buf), target
             ops.quantize_range_bits(buf, c, self.num_bits, q, fixed)
+            if self.entropy:
+                return self._entropy_code(q, c, fixed, z.shape, buf), target
             qt = q[..., :c].permute(0, 3, 1, 2)
             return QuantizedTensor(attach(qt, q), fixed[2], fixed[3], fixed, origin=buf, channels=c), target
         if self.packed:
@@ -376,13 +508,16 @@ class Quantizer(_StaticRange):
             ops.quantize_u8(buf, c, q, qparams, scratch)
         else:
             ops.quantize_bits(buf, c, self.num_bits, q, qparams, scratch)
+        if self.entropy:
+            return self._entropy_code(q, c, qparams, z.shape, buf), target
         qt = q[..., :c].permute(0, 3, 1, 2)
         return QuantizedTensor(attach(qt, q), qparams[2], qparams[3], qparams, origin=buf, channels=c), target
 
 
 class Dequantizer(object):
     """reference :143-153.  A QuantizedTensor of any width goes through the one dequantise kernel (the width lives in its
-    scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``."""
+    scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``; an
+    EntropyBottleneck is decoded and dequantised in one launch and must have been coded at ``num_bits``."""
 
     def __init__(self, num_bits=8):
         _check_bits('Dequantizer', num_bits)
@@ -397,6 +532,15 @@ class Dequantizer(object):
             out = qz.origin if qz.origin is not None else \
                 torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
             ops.unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
+            return attach(out[..., :c].permute(0, 3, 1, 2), out), target
+        if isinstance(qz, EntropyBottleneck):
+            if qz.num_bits != self.num_bits:
+                raise ValueError('Dequantizer(num_bits=%d) was handed a payload entropy-coded at %d bits'
+                                 % (self.num_bits, qz.num_bits))
+            n, c, h, w = qz.shape
+            out = qz.origin if qz.origin is not None else \
+                torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
+            ops.entropy_decode_dequantize(qz.payload, qz.offsets, qz.lengths, qz.qparams, out, c, qz.num_bits)
             return attach(out[..., :c].permute(0, 3, 1, 2), out), target
         if self.num_bits == 16 or not isinstance(qz, QuantizedTensor):
             return qz, target
