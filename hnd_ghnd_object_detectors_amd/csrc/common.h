@@ -52,6 +52,21 @@ __device__ __forceinline__ unsigned fdiv(unsigned x, const FastDiv f) {
   unsigned t = __umulhi(x, f.mul);
   return (t + ((x - t) >> 1)) >> (f.shr - 1);
 }
+// GEMM row m of a convolution -> its output pixel (n, oh, ow); div_ow / div_oh = make_fastdiv of the map's ow / oh
+struct RowPixel {
+  unsigned n, oh, ow;
+};
+__device__ __forceinline__ RowPixel row_pixel(unsigned m, const FastDiv& div_ow, const FastDiv& div_oh, int ow, int oh) {
+  const unsigned t = fdiv(m, div_ow), ow_ = m - t * (unsigned)ow;
+  const unsigned n_ = fdiv(t, div_oh), oh_ = t - n_ * (unsigned)oh;
+  return {n_, oh_, ow_};
+}
+
+// the ReLU-mask nibble of four stored values (hnd_conv_desc.mask_out / mask_bits: bit i = value i is positive)
+template <class V>
+__device__ __forceinline__ uint8_t relu_mask_nibble(const V v) {
+  return (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) | (v[3] > 0.f ? 8 : 0));
+}
 
 // Packed GEMM-operand row r (hnd_pack_weights, hnd_wino*_weights) holds output channel chan_of_row(r): inside every
 // group of 64 rows the four 16-row MFMA tiles are interleaved, so the four accumulator tiles a lane of the implicit-

@@ -26,6 +26,7 @@
 
 #include "common.h"
 #include "conv_epilogue.h"
+#include "vmem_ring.h"
 
 #include <stdlib.h>
 
@@ -33,6 +34,8 @@ namespace {
 
 using hnd::f32x4;
 using hnd::FastDiv;
+using hnd::ring_load;
+using hnd::ring_wait;
 
 struct BresArgs {
   FastDiv div_ow, div_oh;     // m -> (n, oh, ow)
@@ -97,9 +100,8 @@ __global__ void __launch_bounds__(512, 1) bres_kernel(const hnd_conv_desc d, con
   // A row m -> element offset of its input pixel (1x1 taps, no padding: always in range)
   auto a_off = [&](int m) -> unsigned {
     m = m < M ? m : M - 1;
-    const unsigned t = hnd::fdiv((unsigned)m, a.div_ow), ow_ = (unsigned)m - t * (unsigned)d.ow;
-    const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-    return ((n_ * (unsigned)d.h + oh_ * (unsigned)d.sh) * (unsigned)d.w_ + ow_ * (unsigned)d.sw) * (unsigned)d.cin +
+    const hnd::RowPixel q = hnd::row_pixel((unsigned)m, a.div_ow, a.div_oh, d.ow, d.oh);
+    return ((q.n * (unsigned)d.h + q.oh * (unsigned)d.sh) * (unsigned)d.w_ + q.ow * (unsigned)d.sw) * (unsigned)d.cin +
            (unsigned)(g4 * 4);
   };
 
@@ -210,12 +212,11 @@ __global__ void __launch_bounds__(512, 1) bres_kernel(const hnd_conv_desc d, con
           const int m = cc * 64 + lane;
           int po = -1, pr = 0;
           if (m < M) {
-            const unsigned t = hnd::fdiv((unsigned)m, a.div_ow), ow_ = (unsigned)m - t * (unsigned)d.ow;
-            const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-            const int yr = (int)oh_ * d.y_sh + d.y_oh, yc = (int)ow_ * d.y_sw + d.y_ow;
-            po = ((int)n_ * d.yh + yr) * d.yw + yc;
+            const hnd::RowPixel q = hnd::row_pixel((unsigned)m, a.div_ow, a.div_oh, d.ow, d.oh);
+            const int yr = (int)q.oh * d.y_sh + d.y_oh, yc = (int)q.ow * d.y_sw + d.y_ow;
+            po = ((int)q.n * d.yh + yr) * d.yw + yc;
             if (d.res1_mode == 1)
-              pr = ((int)n_ * d.res1_h + (yr * d.res1_h) / d.yh) * d.res1_w + (yc * d.res1_w) / d.yw;
+              pr = ((int)q.n * d.res1_h + (yr * d.res1_h) / d.yh) * d.res1_w + (yc * d.res1_w) / d.yw;
           }
           __builtin_amdgcn_wave_barrier();            // the wave's previous epilogue has read its tables
           rowoff[lane] = po;
@@ -245,21 +246,11 @@ __global__ void __launch_bounds__(512, 1) bres_kernel(const hnd_conv_desc d, con
 //     memory operations retire in issue order, so "at most 28 outstanding" implies the slot has landed; stores or
 //     compiler-issued loads in between only make the wait stronger.  (Audit: tools/audit_bres_asm.py checks in the
 //     disassembly that no instruction touches a ring register between its load and the wait that names it.)
-// ACC = the slot lives in the accumulator half of the register file ("a": VMEM can target it and an MFMA reads its A
-// operand from it).  Half of the ring's slots do: with all 128 ring registers in architectural VGPRs hipcc ran out of
-// those and shuffled just-requested ring registers into AGPRs (copies of data that had not landed yet); with all of
-// them in AGPRs, beside the two accumulator sets, it ran out of these instead.
-template <int OFF, bool ACC>
-__device__ __forceinline__ void ring_load(f32x4& dst, const float* p) {
-  if (ACC) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(dst) : "v"(p), "n"(OFF));
-  else asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF));
-}
-template <int N, bool ACC>
-__device__ __forceinline__ void ring_wait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3) {
-  if (ACC) asm volatile("s_waitcnt vmcnt(%4)" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3) : "n"(N));
-  else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "n"(N));
-}
-
+// The loads and their register-tied waits are vmem_ring.h's ring_load / ring_wait (ACC = the slot lives in the accumulator
+// half of the register file).  Half of the ring's slots do: with all 128 ring registers in architectural VGPRs hipcc ran
+// out of those and shuffled just-requested ring registers into AGPRs (copies of data that had not landed yet); with all
+// of them in AGPRs, beside the two accumulator sets, it ran out of these instead.
+//
 // RES: the epilogue adds `res1` (identity / downsample sum of a Bottleneck, or the nearest-upsampled FPN top-down map):
 // its 16 rows per tile are requested over the tile's k groups KG-8 .. KG-5 -- asm loads into AGPRs in the same in-order
 // stream as the ring, released by hand-counted waits -- and consumed, like the accumulators, during the next tile's
@@ -292,20 +283,18 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
 
   auto a_ptr = [&](int m) -> const float* {
     m = m < M ? m : M - 1;
-    const unsigned t = hnd::fdiv((unsigned)m, a.div_ow), ow_ = (unsigned)m - t * (unsigned)d.ow;
-    const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-    const size_t pix = ((size_t)n_ * d.h + oh_ * (unsigned)d.sh) * (size_t)d.w_ + ow_ * (unsigned)d.sw;
+    const hnd::RowPixel q = hnd::row_pixel((unsigned)m, a.div_ow, a.div_oh, d.ow, d.oh);
+    const size_t pix = ((size_t)q.n * d.h + q.oh * (unsigned)d.sh) * (size_t)d.w_ + q.ow * (unsigned)d.sw;
     return d.x + pix * (size_t)d.cin + (size_t)(g4 * 4);
   };
   // output pixel of row m (-1 beyond M) and the pixel its residual is read from (mode 1: nearest-upsampled res1)
   auto out_pix = [&](int m, int& pr) -> int {
     pr = 0;
     if (m >= M) return -1;
-    const unsigned t = hnd::fdiv((unsigned)m, a.div_ow), ow_ = (unsigned)m - t * (unsigned)d.ow;
-    const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-    const int yr = (int)oh_ * d.y_sh + d.y_oh, yc = (int)ow_ * d.y_sw + d.y_ow;
-    const int po = ((int)n_ * d.yh + yr) * d.yw + yc;
-    pr = d.res1_mode == 1 ? ((int)n_ * d.res1_h + (yr * d.res1_h) / d.yh) * d.res1_w + (yc * d.res1_w) / d.yw : po;
+    const hnd::RowPixel q = hnd::row_pixel((unsigned)m, a.div_ow, a.div_oh, d.ow, d.oh);
+    const int yr = (int)q.oh * d.y_sh + d.y_oh, yc = (int)q.ow * d.y_sw + d.y_ow;
+    const int po = ((int)q.n * d.yh + yr) * d.yw + yc;
+    pr = d.res1_mode == 1 ? ((int)q.n * d.res1_h + (yr * d.res1_h) / d.yh) * d.res1_w + (yc * d.res1_w) / d.yw : po;
     return po;
   };
 
@@ -421,8 +410,7 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
                 const size_t yo = (size_t)(unsigned)prow[mi * 16 + 4 * g4 + s] * (unsigned)d.ldc + col0;
                 *(vecn*)(d.y + yo) = v;
                 if (NI == 4 && d.mask_out)          // ReLU-mask nibble of the stored values (hnd_conv_desc.mask_out)
-                  d.mask_out[yo >> 2] = (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) |
-                                                  (v[3] > 0.f ? 8 : 0));
+                  d.mask_out[yo >> 2] = hnd::relu_mask_nibble(v);
               }
               // this tile's residual rows, consumed one tile later: four per k group over k groups KG-8 .. KG-5, as asm
               // loads in the ring's own in-order stream.  (As compiler-visible loads hipcc waited for them with counts
@@ -479,9 +467,7 @@ __global__ void __launch_bounds__(256, 1) bres2_kernel(const hnd_conv_desc d, co
             }
             const size_t yo = (size_t)(unsigned)prow[mi * 16 + 4 * g4 + s] * (unsigned)d.ldc + col0;
             *(vecn*)(d.y + yo) = v;
-            if (NI == 4 && d.mask_out)
-              d.mask_out[yo >> 2] = (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) |
-                                              (v[3] > 0.f ? 8 : 0));
+            if (NI == 4 && d.mask_out) d.mask_out[yo >> 2] = hnd::relu_mask_nibble(v);
           }
       }
     }

@@ -10,7 +10,7 @@
 //     ahead, parked in registers for eight k groups (see the counter note), written to LDS two stages ahead; ONE
 //     workgroup barrier per stage (64 k = 256 MFMAs per wave, 8192 cycles) instead of one per 16 k;
 //   * A: as in bres2 -- a lane owns row l16 of a 16-row group and 4 consecutive k, one global_load_dwordx4 per (row
-//     group, k group) into a ring 8 k groups deep; out-of-range taps of the 3x3 convs read a page of zeros;
+//     group, k group; vmem_ring.h) into a ring 8 k groups deep; out-of-range taps of the 3x3 convs read a page of zeros;
 //   * the stream never stops: loads run 8 (A) / 16 (B) k groups ahead of the MFMAs ACROSS tile boundaries, a
 //     workgroup walks its tiles back to back and only the epilogue (scale/shift, residuals, mask, ReLU, stores:
 //     conv_epilogue.h, any operand set) sits between two tiles.
@@ -29,6 +29,7 @@
 #include "common.h"
 #include "conv_epilogue.h"
 #include "stream_k_relay.h"
+#include "vmem_ring.h"
 
 #include <stdlib.h>
 
@@ -36,6 +37,8 @@ namespace {
 
 using hnd::f32x4;
 using hnd::FastDiv;
+using hnd::ring_load;
+using hnd::ring_wait;
 using hnd::static_for;
 
 __device__ float g_zero_page[256];     // source of out-of-range taps: 8 k groups x 64 B + 64 B (zero-initialised)
@@ -49,25 +52,6 @@ struct BstreamArgs {
   float* relay;               // stream-K relay workspace (hnd_conv2d_igemm_workspace), or null: tiles round-robin
   int* err;                   // host-visible sticky error word (pinned, mapped): a relay wait that timed out raises it
 };
-
-// ACC: the register lives in the accumulator half of the file (see conv_bres.hip: half of the ring does)
-template <int OFF, bool ACC>
-__device__ __forceinline__ void vload(f32x4& dst, const float* p) {
-  if (ACC) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(dst) : "v"(p), "n"(OFF));
-  else asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF));
-}
-template <int N, bool ACC>
-__device__ __forceinline__ void slot_wait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& b0, f32x4& b1) {
-  if (ACC)
-    asm volatile("s_waitcnt vmcnt(%6)" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3), "+v"(b0), "+v"(b1) : "n"(N));
-  else
-    asm volatile("s_waitcnt vmcnt(%6)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1) : "n"(N));
-}
-template <int N, bool ACC>
-__device__ __forceinline__ void slot_wait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& b0) {
-  if (ACC) asm volatile("s_waitcnt vmcnt(%5)" : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3), "+v"(b0) : "n"(N));
-  else asm volatile("s_waitcnt vmcnt(%5)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0) : "n"(N));
-}
 
 // WN = wave columns: block tile (64 * 4 / WN) x (64 * WN), every wave a 64 x 64 tile of 4 x 4 MFMA tiles.
 // Work split: the stream-K relay (stream_k_relay.h).
@@ -197,20 +181,9 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
 
   // ---- the load streams: A runs one iteration (8 k groups) ahead of the MFMAs, B two (4 stages); both walk the
   // segment list on their own (past its end they stay on the last iteration: harmless extra loads)
-  struct Pos { int seg, it, it1, tile; };
-  auto pos_init = [&](Pos& q) {
-    int kind;
-    q.seg = 0;
-    seg_of(0, q.tile, q.it, q.it1, kind);
-  };
-  auto pos_next = [&](Pos& q) -> bool {                 // true: entered a new segment
-    if (q.it + 1 < q.it1) { ++q.it; return false; }
-    if (q.seg + 1 >= nseg) return false;
-    int kind;
-    ++q.seg;
-    seg_of(q.seg, q.tile, q.it, q.it1, kind);
-    return true;
-  };
+  using Pos = hnd::RelayPos;
+  auto pos_init = [&](Pos& q) { hnd::relay_pos_init(q, seg_of); };
+  auto pos_next = [&](Pos& q) -> bool { return hnd::relay_pos_next(q, nseg, seg_of); };      // true: entered a new segment
   Pos pa, pb;
   pos_init(pa);
   pos_init(pb);
@@ -245,13 +218,13 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
       constexpr bool acc = (u & 1) != 0;
       const float* bl = u < 4 ? bl0 : bl1;
       okr[u] = okb;
-      vload<u * 64, acc>(ring[u][0], lp[0]);
-      vload<u * 64, acc>(ring[u][1], lp[1]);
-      if (NB == 2) vload<0, false>(bst[u][0], bl + (size_t)(2 * u4) * kd16);
-      vload<u * 64, acc>(ring[u][2], lp[2]);
-      vload<u * 64, acc>(ring[u][3], lp[3]);
-      if (NB == 2) vload<0, false>(bst[u][1], bl + (size_t)(2 * u4 + 1) * kd16);
-      else vload<0, false>(bst[u][0], bl + (size_t)u4 * kd16);
+      ring_load<u * 64, acc>(ring[u][0], lp[0]);
+      ring_load<u * 64, acc>(ring[u][1], lp[1]);
+      if (NB == 2) ring_load<0, false>(bst[u][0], bl + (size_t)(2 * u4) * kd16);
+      ring_load<u * 64, acc>(ring[u][2], lp[2]);
+      ring_load<u * 64, acc>(ring[u][3], lp[3]);
+      if (NB == 2) ring_load<0, false>(bst[u][1], bl + (size_t)(2 * u4 + 1) * kd16);
+      else ring_load<0, false>(bst[u][0], bl + (size_t)u4 * kd16);
     });
   }
   if (pos_next(pa)) rows_of(pa.tile / a.ntiles, ra);
@@ -310,8 +283,8 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
         constexpr int u = decltype(U)::value, u4 = u & 3;
         constexpr bool sacc = (u & 1) != 0;
         const float* bl = u < 4 ? bl0 : bl1;
-        if constexpr (NB == 2) slot_wait<VM, sacc>(ring[u][0], ring[u][1], ring[u][2], ring[u][3], bst[u][0], bst[u][1]);
-        else slot_wait<VM, sacc>(ring[u][0], ring[u][1], ring[u][2], ring[u][3], bst[u][0]);
+        if constexpr (NB == 2) ring_wait<VM, sacc>(ring[u][0], ring[u][1], ring[u][2], ring[u][3], bst[u][0], bst[u][1]);
+        else ring_wait<VM, sacc>(ring[u][0], ring[u][1], ring[u][2], ring[u][3], bst[u][0]);
         const unsigned okc = okr[u];
         okr[u] = okb;
         const int wofs = ((rbuf + 2) % NST) * STG + wpos0;
@@ -343,10 +316,10 @@ __global__ void __launch_bounds__(256, 1) bstream_kernel(const hnd_conv_desc d, 
             }
             __builtin_amdgcn_sched_barrier(0);
           }
-          vload<u * 64, sacc>(ring[u][mi], lp[mi]);
-          if (NB == 2 && mi == 1) vload<0, false>(bst[u][0], bl + (size_t)(2 * u4) * kd16);
-          if (NB == 2 && mi == 3) vload<0, false>(bst[u][1], bl + (size_t)(2 * u4 + 1) * kd16);
-          if (NB == 1 && mi == 3) vload<0, false>(bst[u][0], bl + (size_t)u4 * kd16);
+          ring_load<u * 64, sacc>(ring[u][mi], lp[mi]);
+          if (NB == 2 && mi == 1) ring_load<0, false>(bst[u][0], bl + (size_t)(2 * u4) * kd16);
+          if (NB == 2 && mi == 3) ring_load<0, false>(bst[u][1], bl + (size_t)(2 * u4 + 1) * kd16);
+          if (NB == 1 && mi == 3) ring_load<0, false>(bst[u][0], bl + (size_t)u4 * kd16);
           __builtin_amdgcn_sched_barrier(0);
         });
 #pragma unroll

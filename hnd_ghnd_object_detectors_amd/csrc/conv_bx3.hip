@@ -15,15 +15,16 @@
 //
 // Structure = bres2 (conv_bres.hip): one wave per SIMD, the weight slice resident in LDS (three pre-split planes of
 // [64 columns][K], 96 KB at K = 256, XOR-swizzled 16-byte chunks), A fragments straight from global memory through a
-// counted inline-asm register ring 4 k steps deep that runs across tile boundaries, and the split of k step s + 1 riding
-// between the MFMAs of k step s: per accumulator tile six MFMAs (96 matrix-pipe cycles, 48 free for vector issue) and one
-// pair of elements split (11 vector instructions + 2 accumulator-register reads).
+// counted inline-asm register ring (vmem_ring.h) 4 k steps deep that runs across tile boundaries, and the split of k step
+// s + 1 riding between the MFMAs of k step s: per accumulator tile six MFMAs (96 matrix-pipe cycles, 48 free for vector
+// issue) and one pair of elements split (11 vector instructions + 2 accumulator-register reads): bf16x3.h's mfma6_split.
 //
 // Roofline: bf16 MFMA at 6 products = 2.5 PFLOP/s / 6 = 0.42 PFLOP/s-equivalent of fp32 work, 2.7x the fp32 MFMA peak;
 // at K = N = 256 the operands' 4 M (K + N) bytes bound a launch at 0.35 ms of HBM time against 0.34 ms of matrix time.
 
 #include "bf16x3.h"
 #include "common.h"
+#include "vmem_ring.h"
 
 #include <stdlib.h>
 
@@ -33,6 +34,8 @@ using hnd::bf8;
 using hnd::cu_count;
 using hnd::f32x4;
 using hnd::FastDiv;
+using hnd::ring_load;
+using hnd::ring_wait;
 using hnd::split_pair;
 using hnd::static_for;
 using hnd::u32x4;
@@ -47,41 +50,6 @@ struct Bx3Args {
   int cpg;                    // chunks per weight group (Winograd component), 0 = one group
   int res_up;                 // RES: res1 is the exactly 2x coarser map, nearest-upsampled (the FPN's top-down path)
 };
-
-// All ring slots live in the accumulator half of the register file (VMEM can target it; the vector ALU reaches it through
-// v_accvgpr_read): with ring registers among the architectural ones hipcc sat at its limit and moved just-requested
-// registers away before their wait.
-template <int OFF>
-__device__ __forceinline__ void rload(f32x4& dst, const float* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(dst) : "v"(p), "n"(OFF));
-}
-// The register-tied wait of a slot must be ONE statement on every path: tied waits in the two arms of a branch made hipcc
-// merge the ring registers with copies placed BEFORE the wait in one arm.
-template <int CNT>
-__device__ __forceinline__ void rwait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4, f32x4& a5, f32x4& a6,
-                                      f32x4& a7) {
-  asm volatile("s_waitcnt vmcnt(%8)"
-               : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3), "+a"(a4), "+a"(a5), "+a"(a6), "+a"(a7)
-               : "n"(CNT));
-}
-
-__device__ __forceinline__ void bload(uint32_t& dst, const uint8_t* p) {
-  asm volatile("global_load_ubyte %0, %1, off" : "=a"(dst) : "v"(p));
-}
-template <int CNT>
-__device__ __forceinline__ void bwait8(uint32_t& a0, uint32_t& a1, uint32_t& a2, uint32_t& a3, uint32_t& a4, uint32_t& a5,
-                                       uint32_t& a6, uint32_t& a7) {
-  asm volatile("s_waitcnt vmcnt(%8)"
-               : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3), "+a"(a4), "+a"(a5), "+a"(a6), "+a"(a7)
-               : "n"(CNT));
-}
-
-// STORES: global stores per tile (16 rows, + 16 mask bytes with mask_out)
-template <int CNT>
-__device__ __forceinline__ void rwait8(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4, f32x4& a5, f32x4& a6,
-                                       f32x4& a7) {
-  rwait<CNT>(a0, a1, a2, a3, a4, a5, a6, a7);
-}
 
 // KS = K / 32 (4: K = 128, 8: K = 256).  Block = 4 waves, one 64-row chunk each at a time, all on the workgroup's 64 columns.
 // RES: the epilogue adds res1 (same geometry as y: the identity / downsample sum of a Bottleneck).  Its 16 rows per tile
@@ -100,6 +68,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
   // (RES: ring 128 + accumulators 64 + residual rows 64 = all 256 accumulator registers, and hipcc then parks just-requested
   // ring registers elsewhere before their wait; the residual builds run a ring of 2 -- their A operand was written by the
   // previous launch and comes from the memory-side cache)
+  // STORES: global stores per tile (16 rows, + 16 mask bytes with mask_out)
   constexpr int RING = RES ? 2 : 4, K = 32 * KS, MI = 4, NI = 4, PLANE = 64 * K, STORES = MO ? 32 : 16;
   static_assert(KS % RING == 0, "ring slots are compile-time: the ring must divide the k steps of a tile");
   extern __shared__ __attribute__((aligned(16))) uint16_t Bs[];       // [3 planes][64 rows][K]
@@ -115,9 +84,8 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
   // A row m -> its first element (1x1 taps, no padding: always in range); 8 consecutive k per lane and k step
   auto a_ptr = [&](int cc, int mi) -> const float* {
     const unsigned m = min((unsigned)(cc * 64 + mi * 16 + l16), (unsigned)(a.mrows - 1));
-    const unsigned t = hnd::fdiv(m, a.div_ow), ow_ = m - t * (unsigned)d.ow;
-    const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-    const size_t pix = ((size_t)n_ * d.h + oh_ * (unsigned)d.sh) * (size_t)d.w_ + ow_ * (unsigned)d.sw;
+    const hnd::RowPixel q = hnd::row_pixel(m, a.div_ow, a.div_oh, d.ow, d.oh);
+    const size_t pix = ((size_t)q.n * d.h + q.oh * (unsigned)d.sh) * (size_t)d.w_ + q.ow * (unsigned)d.sw;
     return d.x + pix * (size_t)d.cin + (size_t)(g4 * 8);
   };
   // epilogue constants of the lane's 4 consecutive channels (hnd::chan_of_row of its packed rows)
@@ -162,8 +130,8 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
         static_for<MI>([&](auto I) __attribute__((always_inline)) {
           constexpr int mi = decltype(I)::value;
           // (KS == RING: every k step of the first tile is requested here)
-          rload<(u % KS) * 128>(ring[u][mi][0], aptr[mi]);
-          rload<(u % KS) * 128 + 16>(ring[u][mi][1], aptr[mi]);
+          ring_load<(u % KS) * 128>(ring[u][mi][0], aptr[mi]);
+          ring_load<(u % KS) * 128 + 16>(ring[u][mi][1], aptr[mi]);
         });
       });
       uint32_t pl[2][3][MI][4];                 // [parity][hi / mid / lo][row group]: 4 dwords = 8 bf16
@@ -177,7 +145,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
       float dummy = 0.f;
 #pragma unroll
       for (int i = 0; i < STORES; ++i) asm volatile("global_load_dword %0, %1, off" : "+v"(dummy) : "v"(aptr[0]));
-      rwait<8 * (RING - 1) + STORES>(ring[0][0][0], ring[0][0][1], ring[0][1][0], ring[0][1][1], ring[0][2][0], ring[0][2][1],
+      ring_wait<8 * (RING - 1) + STORES>(ring[0][0][0], ring[0][0][1], ring[0][1][0], ring[0][1][1], ring[0][2][0], ring[0][2][1],
                                      ring[0][3][0], ring[0][3][1]);
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi)
@@ -210,7 +178,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
             for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
               for (int r = 0; r < 4; ++r)
-                bload(resm[mi][r], d.mask_bits + (((size_t)min(cc * 64 + mi * 16 + g4 * 4 + r, a.mrows - 1) * (size_t)d.ldc + col0) >> 2));
+                hnd::ring_load_byte(resm[mi][r], d.mask_bits + (((size_t)min(cc * 64 + mi * 16 + g4 * 4 + r, a.mrows - 1) * (size_t)d.ldc + col0) >> 2));
           }
           if constexpr (RES && ks == KS - 4) {
 #pragma unroll
@@ -221,28 +189,27 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
               // a row and start at an even column): pixel (n, y, x) reads (n, y / 2, x / 2).  Both addresses are computed
               // and one is SELECTED, so that the asm loads sit in one straight block whatever the mode (an if / else here
               // comes out as two correlated branches, which tools/audit_bres_asm.py cannot follow)
-              const unsigned t = hnd::fdiv(m0, a.div_ow), ow_ = m0 - t * (unsigned)d.ow;
-              const unsigned n_ = hnd::fdiv(t, a.div_oh), oh_ = t - n_ * (unsigned)d.oh;
-              const size_t pu = ((size_t)n_ * d.res1_h + (oh_ >> 1)) * (size_t)d.res1_w + (ow_ >> 1);
+              const hnd::RowPixel q = hnd::row_pixel(m0, a.div_ow, a.div_oh, d.ow, d.oh);
+              const size_t pu = ((size_t)q.n * d.res1_h + (q.oh >> 1)) * (size_t)d.res1_w + (q.ow >> 1);
               const bool up = a.res_up != 0;
               const unsigned ml = (unsigned)(a.mrows - 1);
               const size_t p0 = up ? pu : (size_t)min(mr, ml), p1 = up ? pu : (size_t)min(mr + 1, ml),
                            p2 = up ? pu + 1 : (size_t)min(mr + 2, ml), p3 = up ? pu + 1 : (size_t)min(mr + 3, ml);
-              rload<0>(resv[mi][0], d.res1 + p0 * (size_t)d.ldc + col0);
-              rload<0>(resv[mi][1], d.res1 + p1 * (size_t)d.ldc + col0);
-              rload<0>(resv[mi][2], d.res1 + p2 * (size_t)d.ldc + col0);
-              rload<0>(resv[mi][3], d.res1 + p3 * (size_t)d.ldc + col0);
+              ring_load<0>(resv[mi][0], d.res1 + p0 * (size_t)d.ldc + col0);
+              ring_load<0>(resv[mi][1], d.res1 + p1 * (size_t)d.ldc + col0);
+              ring_load<0>(resv[mi][2], d.res1 + p2 * (size_t)d.ldc + col0);
+              ring_load<0>(resv[mi][3], d.res1 + p3 * (size_t)d.ldc + col0);
             }
           }
           // slot `slot` was split during the previous step: refill it for the step RING ahead (this tile or the next)
           static_for<MI>([&](auto I) __attribute__((always_inline)) {
             constexpr int mi = decltype(I)::value;
             if constexpr (ks + RING < KS) {
-              rload<(ks + RING) * 128>(ring[slot][mi][0], aptr[mi]);
-              rload<(ks + RING) * 128 + 16>(ring[slot][mi][1], aptr[mi]);
+              ring_load<(ks + RING) * 128>(ring[slot][mi][0], aptr[mi]);
+              ring_load<(ks + RING) * 128 + 16>(ring[slot][mi][1], aptr[mi]);
             } else {
-              rload<(ks + RING - KS) * 128>(ring[slot][mi][0], nptr[mi]);
-              rload<(ks + RING - KS) * 128 + 16>(ring[slot][mi][1], nptr[mi]);
+              ring_load<(ks + RING - KS) * 128>(ring[slot][mi][0], nptr[mi]);
+              ring_load<(ks + RING - KS) * 128 + 16>(ring[slot][mi][1], nptr[mi]);
             }
           });
           // The next step's slot was requested RING - 1 steps ago: 8 (RING - 1) younger ring loads may be in flight, plus
@@ -251,11 +218,11 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
           constexpr int kResYounger = (RES && ks >= KS - 4 && ks <= KS - 4 + RING - 2) ? RESLOADS : 0;
           if constexpr (ks < RING - 1) {
             // (the counter holds 6 bits: a larger allowance is clipped to 63 -- a stronger, still correct wait)
-            rwait<(8 * (RING - 1) + STORES + kResYounger < 63 ? 8 * (RING - 1) + STORES + kResYounger : 63)>(
+            ring_wait<(8 * (RING - 1) + STORES + kResYounger < 63 ? 8 * (RING - 1) + STORES + kResYounger : 63)>(
                 ring[slot1][0][0], ring[slot1][0][1], ring[slot1][1][0], ring[slot1][1][1], ring[slot1][2][0],
                 ring[slot1][2][1], ring[slot1][3][0], ring[slot1][3][1]);
           } else {
-            rwait<8 * (RING - 1) + kResYounger>(ring[slot1][0][0], ring[slot1][0][1], ring[slot1][1][0], ring[slot1][1][1],
+            ring_wait<8 * (RING - 1) + kResYounger>(ring[slot1][0][0], ring[slot1][0][1], ring[slot1][1][0], ring[slot1][1][1],
                                                 ring[slot1][2][0], ring[slot1][2][1], ring[slot1][3][0], ring[slot1][3][1]);
           }
           const int pos = ((ks * 4 + g4) ^ l16) * 8;
@@ -283,24 +250,8 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
               const f32x4 v = ring[slot1][rg][j >> 1];
               const float x0 = (j & 1) ? v.z : v.x, x1 = (j & 1) ? v.w : v.y;
               f32x4 cacc = (ks == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : acc[mi][ni];
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bcur[0], cacc, 0, 0, 0);      // smallest terms first
-              const uint32_t h0 = __float_as_uint(x0) & 0xffff0000u, h1 = __float_as_uint(x1) & 0xffff0000u;
-              __builtin_amdgcn_sched_barrier(0);
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[2], cacc, 0, 0, 0);
-              const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-              __builtin_amdgcn_sched_barrier(0);
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bcur[1], cacc, 0, 0, 0);
-              const uint32_t m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-              __builtin_amdgcn_sched_barrier(0);
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bcur[0], cacc, 0, 0, 0);
-              const float q0 = r0 - __uint_as_float(m0), q1 = r1 - __uint_as_float(m1);
-              __builtin_amdgcn_sched_barrier(0);
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[1], cacc, 0, 0, 0);
-              pl[par ^ 1][0][rg][j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-              pl[par ^ 1][1][rg][j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-              pl[par ^ 1][2][rg][j] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-              __builtin_amdgcn_sched_barrier(0);
-              cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[0], cacc, 0, 0, 0);
+              hnd::mfma6_split(cacc, ah, am, al, bcur, x0, x1, pl[par ^ 1][0][rg][j], pl[par ^ 1][1][rg][j],
+                               pl[par ^ 1][2][rg][j]);
               acc[mi][ni] = cacc;
               __builtin_amdgcn_sched_barrier(0);
             });
@@ -309,11 +260,11 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
         });
         // the tile's residual rows: requested at k step KS - 4, the 4 x 8 refills of steps KS - 4 .. KS - 1 came after them
         if constexpr (RES) {
-          rwait8<32>(resv[0][0], resv[0][1], resv[0][2], resv[0][3], resv[1][0], resv[1][1], resv[1][2], resv[1][3]);
-          rwait8<32>(resv[2][0], resv[2][1], resv[2][2], resv[2][3], resv[3][0], resv[3][1], resv[3][2], resv[3][3]);
+          ring_wait<32>(resv[0][0], resv[0][1], resv[0][2], resv[0][3], resv[1][0], resv[1][1], resv[1][2], resv[1][3]);
+          ring_wait<32>(resv[2][0], resv[2][1], resv[2][2], resv[2][3], resv[3][0], resv[3][1], resv[3][2], resv[3][3]);
           if constexpr (MK) {                        // (older than the residual rows: landed with them)
-            bwait8<32>(resm[0][0], resm[0][1], resm[0][2], resm[0][3], resm[1][0], resm[1][1], resm[1][2], resm[1][3]);
-            bwait8<32>(resm[2][0], resm[2][1], resm[2][2], resm[2][3], resm[3][0], resm[3][1], resm[3][2], resm[3][3]);
+            ring_wait<32>(resm[0][0], resm[0][1], resm[0][2], resm[0][3], resm[1][0], resm[1][1], resm[1][2], resm[1][3]);
+            ring_wait<32>(resm[2][0], resm[2][1], resm[2][2], resm[2][3], resm[3][0], resm[3][1], resm[3][2], resm[3][3]);
           }
         }
         // the tile's 16 row stores: C/D layout row = 4 g4 + reg of a 16-row group, column = l16 -> channels col0 .. col0 + 3;
@@ -333,9 +284,7 @@ __global__ void __launch_bounds__(256, 1) bx3_kernel(const hnd_conv_desc d, cons
             }
             const size_t yo = m * (size_t)d.ldc + col0;
             *(f32x4*)(d.y + yo) = v;
-            if (MO)
-              d.mask_out[yo >> 2] = (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) |
-                                              (v[3] > 0.f ? 8 : 0));
+            if (MO) d.mask_out[yo >> 2] = hnd::relu_mask_nibble(v);
           }
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) aptr[mi] = nptr[mi];
@@ -358,16 +307,10 @@ __global__ void pack_bx3_kernel(const float* __restrict__ w, uint16_t* __restric
     long long t = e / K;
     const int row = (int)(t % rows_pad), g = (int)(t / rows_pad);
     const float x = w[(size_t)g * (size_t)group_stride + (size_t)row * K + k];
-    const uint32_t xb = __float_as_uint(x), hb = xb & 0xffff0000u;
-    const float r1 = x - __uint_as_float(hb);
-    const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(mb);
     const int part = k / KI, kk = k - part * KI;
     const int s = row / 64, r = row % 64, c = kk >> 3, pos = c ^ (r & 15);
     uint16_t* o = img + (((size_t)part * groups + g) * nsl + s) * 3 * plane + (size_t)r * KI + pos * 8 + (kk & 7);
-    o[0] = (uint16_t)(hb >> 16);
-    o[plane] = (uint16_t)(mb >> 16);
-    o[2 * plane] = (uint16_t)(__float_as_uint(r2) >> 16);
+    hnd::split_value(x, o[0], o[plane], o[2 * plane]);
   }
 }
 
@@ -534,10 +477,6 @@ extern "C" int hnd_pack_bf16x3(const float* w_packed, uint16_t* img, int rows_pa
   HND_REQUIRE(w_packed && img && rows_pad > 0 && rows_pad % 64 == 0 && (kdim == 128 || (kdim % 256 == 0 && kdim <= 2048)) &&
                   groups >= 1 && (groups == 1 || group_stride >= (int64_t)rows_pad * kdim),
               "hnd_pack_bf16x3: bad arguments (kdim must be 128 or a multiple of 256 up to 2048)");
-  const long long total = (long long)groups * rows_pad * kdim;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pack_bx3_kernel, dim3((unsigned)blocks), dim3(256), 0, hnd::as_stream(stream), w_packed, img, rows_pad,
-                     kdim, kdim > 256 ? 256 : kdim, groups, (long long)group_stride, total);
-  return hnd::check_launch("hnd_pack_bf16x3");
+  return hnd::launch_pack(pack_bx3_kernel, (long long)groups * rows_pad * kdim, stream, "hnd_pack_bf16x3", w_packed, img,
+                          rows_pad, kdim, kdim > 256 ? 256 : kdim, groups, (long long)group_stride);
 }

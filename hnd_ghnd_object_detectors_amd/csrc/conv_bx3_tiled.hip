@@ -4,7 +4,8 @@
 // is hidden by occupancy instead of a hand-counted register ring.  Everything here is compiler-visible loads + LDS.
 //
 // SAME BITS as bx3_kernel (DESIGN section 4 rule 4) -- what that rests on:
-//   * operands split by the family's one split_pair (bf16x3.h; the weight image is the persistent build's own);
+//   * operands split by the family's one split_pair and multiplied by its one six-product step, mfma6 (bf16x3.h; the weight
+//     image is the persistent build's own);
 //   * the same v_mfma_f32_16x16x32_bf16 with every k value in the lane and element position it has there: lane l16 = row (A) /
 //     column (B) of the 16-wide tile, lane group g4 holds k = 32 ks + 8 g4 .. + 7;
 //   * per 32-k step the six products lo.hi, hi.lo, mid.mid, mid.hi, hi.mid, hi.hi, k steps ascending, a fresh accumulator per
@@ -150,18 +151,9 @@ __global__ void __launch_bounds__(256, MI == 1 ? 3 : 2) bx3t_kernel(const hnd_co
       for (int ni = 0; ni < NI; ++ni) {
         const int row = ni * 16 + l16;
         const uint16_t* br = B + row * KP + (((ksl * 4 + g4) ^ ((row >> 1) & 7)) * 8);
-        const bf8 bh = *(const bf8*)(br), bm = *(const bf8*)(br + PPLANE), bl = *(const bf8*)(br + 2 * PPLANE);
+        const bf8 b[3] = {*(const bf8*)(br), *(const bf8*)(br + PPLANE), *(const bf8*)(br + 2 * PPLANE)};      // hi, mid, lo
 #pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          f32x4 c = acc[mi][ni];
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[mi], bh, c, 0, 0, 0);      // smallest terms first
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mi], bl, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[mi], bm, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[mi], bh, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mi], bm, c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[mi], bh, c, 0, 0, 0);
-          acc[mi][ni] = c;
-        }
+        for (int mi = 0; mi < MI; ++mi) hnd::mfma6(acc[mi][ni], ah[mi], am[mi], al[mi], b);
       }
     }
     if (more) store_b((pc + 1) & 1);      // (last read during piece pc - 1: every wave is past the barrier that closed it)
@@ -222,9 +214,7 @@ __global__ void __launch_bounds__(256, MI == 1 ? 3 : 2) bx3t_kernel(const hnd_co
         v[ni] = d.relu ? fmaxf(x, 0.f) : x;
       }
       *(f32x4*)(d.y + yo) = v;
-      if (d.mask_out)
-        d.mask_out[yo >> 2] =
-            (uint8_t)((v[0] > 0.f ? 1 : 0) | (v[1] > 0.f ? 2 : 0) | (v[2] > 0.f ? 4 : 0) | (v[3] > 0.f ? 8 : 0));
+      if (d.mask_out) d.mask_out[yo >> 2] = hnd::relu_mask_nibble(v);
     }
 }
 

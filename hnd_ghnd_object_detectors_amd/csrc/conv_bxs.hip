@@ -2,16 +2,16 @@
 // emulation kernel (conv_bx3.hip) cannot take -- convolutions over TAPS (the stride-2 3x3 convs of layers 2-4 and the parity
 // launches of their data gradients, the head's direct 2x2 convs with BatchNorm(+ReLU) on load and BatchNorm statistics /
 // backward sums in the epilogue), long K (1x1 convs of layer4, K = 2048), strided outputs (the downsample data gradients)
-// and fp32 masks.  Arithmetic = conv_bx3.hip's (every fp32 operand the exact sum of three bf16 planes by truncation, the six
-// plane products with i + j <= 2 on v_mfma_f32_16x16x32_bf16, smallest terms first inside every 32-deep k step, fp32
-// accumulate; k steps ascending over (tap, channel)); structure = conv_bstream.hip's:
+// and fp32 masks.  Arithmetic = the family's, written once in bf16x3.h (every fp32 operand the exact sum of three bf16
+// planes by truncation, the six plane products with i + j <= 2 on v_mfma_f32_16x16x32_bf16, smallest terms first inside
+// every 32-deep k step, fp32 accumulate; k steps ascending over (tap, channel)); structure = conv_bstream.hip's:
 //   * B: the pre-split weight image (hnd_pack_bf16x3s: per 64-column slice and 64-k stage three planes of [64 rows][64 k]
-//     bf16, XOR-swizzled 16-byte chunks) streams through THREE LDS stages by LDS-DMA (global_load_lds_dwordx4: 1 KB per wave
+//     bf16, XOR-swizzled 16-byte chunks) streams through THREE LDS stages by LDS-DMA (vmem_ring.h's glds16: 1 KB per wave
 //     instruction, no registers), requested two stages ahead; one workgroup barrier per stage (64 k = 192 MFMAs per wave);
 //   * A: fp32 straight from global memory, a lane owns row l16 of a 16-row group and 8 consecutive k of a 32-deep step (two
-//     global_load_dwordx4 into the accumulator half of the register file), ring of 4 k steps = one 128-k iteration ahead;
+//     vmem_ring.h ring loads into the accumulator half of the register file), ring of 4 k steps = one 128-k iteration ahead;
 //     out-of-range taps read a page of zeros; the BatchNorm(+ReLU) prologue is applied during the split (padding stays 0);
-//   * the split of k step s + 1 into bf16 planes rides between the MFMAs of k step s (conv_bx3.hip);
+//   * the split of k step s + 1 into bf16 planes rides between the MFMAs of k step s (bf16x3.h: mfma6_split);
 //     (measured and not kept, round 6: the stage's DMA pieces issued one per MFMA tile instead of at the top of the step --
 //     4 % slower; the next step's first B fragments read a step early -- nothing)
 //   * tiles 128 x 128 (two wave columns) or 256 x 64, every wave 64 x 64; the stream-K relay (stream_k_relay.h: a
@@ -26,6 +26,7 @@
 #include "common.h"
 #include "conv_epilogue.h"
 #include "stream_k_relay.h"
+#include "vmem_ring.h"
 
 #include <stdlib.h>
 
@@ -34,6 +35,9 @@ namespace {
 using hnd::bf8;
 using hnd::f32x4;
 using hnd::FastDiv;
+using hnd::glds16;
+using hnd::ring_load;
+using hnd::ring_wait;
 using hnd::static_for;
 using hnd::u32x4;
 
@@ -48,27 +52,6 @@ struct BxsArgs {
   float* relay;               // stream-K relay workspace (hnd_conv2d_igemm_workspace), or null: tiles round-robin
   int* err;                   // host-visible sticky error word
 };
-
-// ring slots live in the accumulator half of the register file (conv_bx3.hip)
-template <int OFF>
-__device__ __forceinline__ void aload(f32x4& dst, const float* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(dst) : "v"(p), "n"(OFF));
-}
-template <int CNT>
-__device__ __forceinline__ void await8(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3, f32x4& a4, f32x4& a5, f32x4& a6, f32x4& a7) {
-  asm volatile("s_waitcnt vmcnt(%8)"
-               : "+a"(a0), "+a"(a1), "+a"(a2), "+a"(a3), "+a"(a4), "+a"(a5), "+a"(a6), "+a"(a7)
-               : "n"(CNT));
-}
-// LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses to lds_dst + 16 * lane (M0 is compiler-reserved: saved,
-// written and restored inside the one statement)
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(gsrc), "s"(lds_dst)
-               : "memory");
-}
 
 // WN = wave columns: block tile (64 * 4 / WN) x (64 * WN), every wave a 64 x 64 tile of 4 x 4 MFMA tiles.
 // PRO: BatchNorm(+ReLU) of the input on load (pro_scale / pro_shift per input channel); TAPS: kh * kw > 1 or padding.
@@ -216,20 +199,9 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
 
   // ---- the load stream runs ONE iteration (128 k: 4 k steps, 2 stages) ahead of the MFMAs and walks the segment list on
   // its own (past its end it stays on the last iteration: harmless extra loads)
-  struct Pos { int seg, it, it1, tile; };
-  auto pos_init = [&](Pos& q) {
-    int kind;
-    q.seg = 0;
-    seg_of(0, q.tile, q.it, q.it1, kind);
-  };
-  auto pos_next = [&](Pos& q) -> bool {                 // true: entered a new segment
-    if (q.it + 1 < q.it1) { ++q.it; return false; }
-    if (q.seg + 1 >= nseg) return false;
-    int kind;
-    ++q.seg;
-    seg_of(q.seg, q.tile, q.it, q.it1, kind);
-    return true;
-  };
+  using Pos = hnd::RelayPos;
+  auto pos_init = [&](Pos& q) { hnd::relay_pos_init(q, seg_of); };
+  auto pos_next = [&](Pos& q) -> bool { return hnd::relay_pos_next(q, nseg, seg_of); };      // true: entered a new segment
   Pos pn;
   pos_init(pn);
   Rows rn;
@@ -251,8 +223,8 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
     if constexpr (u == 2 && !BIG) b_issue(bt, 2 * pn.it + 1, 1);
     static_for<MI>([&](auto I) __attribute__((always_inline)) {
       constexpr int mi = decltype(I)::value;
-      aload<o>(ring[u][mi][0], lpn[hf][mi]);
-      aload<o + 16>(ring[u][mi][1], lpn[hf][mi]);
+      ring_load<o>(ring[u][mi][0], lpn[hf][mi]);
+      ring_load<o + 16>(ring[u][mi][1], lpn[hf][mi]);
     });
   });
 #pragma unroll
@@ -292,7 +264,7 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the prologue table is complete
   }
   // step 0 of the first iteration: split before the loop (a wait in the place of step "-1")
-  await8<BIG ? W_BIG_3 : W_ODD>(ring[0][0][0], ring[0][0][1], ring[0][1][0], ring[0][1][1], ring[0][2][0], ring[0][2][1],
+  ring_wait<BIG ? W_BIG_3 : W_ODD>(ring[0][0][0], ring[0][0][1], ring[0][1][0], ring[0][1][1], ring[0][2][0], ring[0][2][1],
                                 ring[0][3][0], ring[0][3][1]);
   pro_fetch(chc[0]);
 #pragma unroll
@@ -353,10 +325,10 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
         // slot u was split during the previous step: refill it with step u of the next iteration
         static_for<MI>([&](auto I) __attribute__((always_inline)) {
           constexpr int mi = decltype(I)::value;
-          aload<par * 128>(ring[u][mi][0], lpn[hf][mi]);
-          aload<par * 128 + 16>(ring[u][mi][1], lpn[hf][mi]);
+          ring_load<par * 128>(ring[u][mi][0], lpn[hf][mi]);
+          ring_load<par * 128 + 16>(ring[u][mi][1], lpn[hf][mi]);
         });
-        await8<BIG ? (u == 3 ? W_BIG_3 : W_BIG_012) : ((u & 1) ? W_ODD : W_EVEN)>(ring[u1][0][0], ring[u1][0][1], ring[u1][1][0], ring[u1][1][1], ring[u1][2][0],
+        ring_wait<BIG ? (u == 3 ? W_BIG_3 : W_BIG_012) : ((u & 1) ? W_ODD : W_EVEN)>(ring[u1][0][0], ring[u1][0][1], ring[u1][1][0], ring[u1][1][1], ring[u1][2][0],
                                          ring[u1][2][1], ring[u1][3][0], ring[u1][3][1]);
         // the step being split (u + 1 of this iteration, or step 0 of the next): its prologue constants and tap validity
         constexpr int hs = ((u + 1) >> 1) & 1;            // half of the iteration the split step lies in
@@ -388,24 +360,8 @@ __global__ void __launch_bounds__(256, 1) bxs_kernel(const hnd_conv_desc d, cons
             const bool ok = (oks >> rg) & 1;
             const float x0 = pro_apply((j & 1) ? v.z : v.x, 2 * j, ok), x1 = pro_apply((j & 1) ? v.w : v.y, 2 * j + 1, ok);
             f32x4 cacc = acc[mi][ni];
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bcur[0], cacc, 0, 0, 0);      // smallest terms first
-            const uint32_t h0 = __float_as_uint(x0) & 0xffff0000u, h1 = __float_as_uint(x1) & 0xffff0000u;
-            __builtin_amdgcn_sched_barrier(0);
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[2], cacc, 0, 0, 0);
-            const float r0 = x0 - __uint_as_float(h0), r1 = x1 - __uint_as_float(h1);
-            __builtin_amdgcn_sched_barrier(0);
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bcur[1], cacc, 0, 0, 0);
-            const uint32_t m0 = __float_as_uint(r0) & 0xffff0000u, m1 = __float_as_uint(r1) & 0xffff0000u;
-            __builtin_amdgcn_sched_barrier(0);
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, bcur[0], cacc, 0, 0, 0);
-            const float q0 = r0 - __uint_as_float(m0), q1 = r1 - __uint_as_float(m1);
-            __builtin_amdgcn_sched_barrier(0);
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[1], cacc, 0, 0, 0);
-            pl[par ^ 1][0][rg][j] = __builtin_amdgcn_perm(h1, h0, 0x07060302u);
-            pl[par ^ 1][1][rg][j] = __builtin_amdgcn_perm(m1, m0, 0x07060302u);
-            pl[par ^ 1][2][rg][j] = __builtin_amdgcn_perm(__float_as_uint(q1), __float_as_uint(q0), 0x07060302u);
-            __builtin_amdgcn_sched_barrier(0);
-            cacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bcur[0], cacc, 0, 0, 0);
+            hnd::mfma6_split(cacc, ah, am, al, bcur, x0, x1, pl[par ^ 1][0][rg][j], pl[par ^ 1][1][rg][j],
+                             pl[par ^ 1][2][rg][j]);
             acc[mi][ni] = cacc;
             __builtin_amdgcn_sched_barrier(0);
           });
@@ -484,15 +440,9 @@ __global__ void pack_bxs_kernel(const float* __restrict__ w, uint16_t* __restric
     long long t = e / K;
     const int row = (int)(t % rows_pad), g = (int)(t / rows_pad);
     const float x = w[(size_t)g * (size_t)group_stride + (size_t)row * K + k];
-    const uint32_t xb = __float_as_uint(x), hb = xb & 0xffff0000u;
-    const float r1 = x - __uint_as_float(hb);
-    const uint32_t mb = __float_as_uint(r1) & 0xffff0000u;
-    const float r2 = r1 - __uint_as_float(mb);
     const int s = row / 64, r = row % 64, st = k / 64, kk = k % 64, c = kk >> 3, pos = c ^ ((r >> 1) & 7);
     uint16_t* o = img + ((((size_t)g * nsl + s) * nst + st) * 3) * 4096 + (size_t)r * 64 + pos * 8 + (kk & 7);
-    o[0] = (uint16_t)(hb >> 16);
-    o[4096] = (uint16_t)(mb >> 16);
-    o[8192] = (uint16_t)(__float_as_uint(r2) >> 16);
+    hnd::split_value(x, o[0], o[4096], o[8192]);
   }
 }
 
@@ -578,10 +528,6 @@ extern "C" int hnd_pack_bf16x3s(const float* w_packed, uint16_t* img, int rows_p
   HND_REQUIRE(w_packed && img && rows_pad > 0 && rows_pad % 64 == 0 && kdim > 0 && kdim % 128 == 0 && groups >= 1 &&
                   (groups == 1 || group_stride >= (int64_t)rows_pad * kdim),
               "hnd_pack_bf16x3s: bad arguments (rows_pad %% 64, kdim %% 128)");
-  const long long total = (long long)groups * rows_pad * kdim;
-  long long blocks = (total + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(pack_bxs_kernel, dim3((unsigned)blocks), dim3(256), 0, hnd::as_stream(stream), w_packed, img, rows_pad,
-                     kdim, groups, (long long)group_stride, total);
-  return hnd::check_launch("hnd_pack_bf16x3s");
+  return hnd::launch_pack(pack_bxs_kernel, (long long)groups * rows_pad * kdim, stream, "hnd_pack_bf16x3s", w_packed, img,
+                          rows_pad, kdim, groups, (long long)group_stride);
 }

@@ -25,6 +25,7 @@
 // Roofline: fp32 MFMA (157.3 TFLOP/s); 2 M cout kh kw cin flop per launch.  Operand traffic per workgroup and k-step:
 // 4 pixels x (128 AH + 128 BH) channels x 4 B = 4 KB per 2048 cycles at 256 x 256 -- 2 B / clk / CU.
 #include "common.h"
+#include "vmem_ring.h"
 
 #include <stdlib.h>
 
@@ -47,23 +48,7 @@ struct WringArgs {
   int splits;
 };
 
-template <int OFF>
-__device__ __forceinline__ void rload(f32x4& dst, const float* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF));
-}
-template <int N>
-__device__ __forceinline__ void rwait(f32x4& a0, f32x4& a1) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(a0), "+v"(a1) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void rwait(f32x4& a0, f32x4& a1, f32x4& a2) {
-  asm volatile("s_waitcnt vmcnt(%3)" : "+v"(a0), "+v"(a1), "+v"(a2) : "n"(N));
-}
-template <int N>
-__device__ __forceinline__ void rwait(f32x4& a0, f32x4& a1, f32x4& a2, f32x4& a3) {
-  asm volatile("s_waitcnt vmcnt(%4)" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "n"(N));
-}
-
+// ring loads and their tied waits: vmem_ring.h (every slot in architectural registers here)
 // AH / BH: 64-channel halves of a wave's tile along cout / along the columns.  TAPS: columns are (tap, ci) of a conv with
 // kh * kw > 1 or padding, each 64-column half inside ONE tap (cin % 64 == 0); else a 1x1 problem (x pixel = dy pixel).
 // WPS: workgroups per CU = waves per SIMD.  The 1x1 problems run one wave per SIMD on 128-row wave tiles (all the vector
@@ -178,12 +163,12 @@ __global__ void __launch_bounds__(256, WPS) wgrad_ring_kernel(const WringArgs a)
     unsigned okb;
     addr(pa, pbv, okb);
     okr[u] = okb;
-    rload<0>(ra[u][0], pa);
-    if constexpr (AH == 2) rload<256>(ra[u][1], pa);
-    rload<0>(rb[u][0], pbv[0]);
+    hnd::ring_load<0, false>(ra[u][0], pa);
+    if constexpr (AH == 2) hnd::ring_load<256, false>(ra[u][1], pa);
+    hnd::ring_load<0, false>(rb[u][0], pbv[0]);
     if constexpr (BH == 2) {
-      if constexpr (TAPS) rload<0>(rb[u][1], pbv[1]);
-      else rload<256>(rb[u][1], pbv[0]);
+      if constexpr (TAPS) hnd::ring_load<0, false>(rb[u][1], pbv[1]);
+      else hnd::ring_load<256, false>(rb[u][1], pbv[0]);
     }
   };
 
@@ -198,10 +183,10 @@ __global__ void __launch_bounds__(256, WPS) wgrad_ring_kernel(const WringArgs a)
     for (int b = 0; b < nblk * (8 / RING); ++b) {            // a block = 8 k-steps = 8 / RING turns of the ring
       hnd::static_for<RING>([&](auto U) __attribute__((always_inline)) {
         constexpr int u = decltype(U)::value;
-        if constexpr (NL == 2) rwait<VM>(ra[u][0], rb[u][0]);
-        else if constexpr (NL == 3 && AH == 2) rwait<VM>(ra[u][0], ra[u][1], rb[u][0]);
-        else if constexpr (NL == 3) rwait<VM>(ra[u][0], rb[u][0], rb[u][1]);
-        else rwait<VM>(ra[u][0], ra[u][1], rb[u][0], rb[u][1]);
+        if constexpr (NL == 2) hnd::ring_wait<VM, false>(ra[u][0], rb[u][0]);
+        else if constexpr (NL == 3 && AH == 2) hnd::ring_wait<VM, false>(ra[u][0], ra[u][1], rb[u][0]);
+        else if constexpr (NL == 3) hnd::ring_wait<VM, false>(ra[u][0], rb[u][0], rb[u][1]);
+        else hnd::ring_wait<VM, false>(ra[u][0], ra[u][1], rb[u][0], rb[u][1]);
         f32x4 bv[BH];
 #pragma unroll
         for (int h = 0; h < BH; ++h) {

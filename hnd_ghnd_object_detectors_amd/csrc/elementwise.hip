@@ -444,7 +444,7 @@ __global__ void affine_relu_kernel(const float* __restrict__ x, const float* __r
       if (relu) { r.x = fmaxf(r.x, 0.f); r.y = fmaxf(r.y, 0.f); r.z = fmaxf(r.z, 0.f); r.w = fmaxf(r.w, 0.f); }
       *(f32x4*)(y + e * 4) = r;
       if (mask_out)     // ReLU-mask nibble of these four channels (hnd_conv_desc.mask_out's layout)
-        mask_out[e] = (uint8_t)((r.x > 0.f ? 1 : 0) | (r.y > 0.f ? 2 : 0) | (r.z > 0.f ? 4 : 0) | (r.w > 0.f ? 8 : 0));
+        mask_out[e] = hnd::relu_mask_nibble(r);
     }
   }
 }
@@ -461,8 +461,7 @@ __global__ void relu_mask_nibbles_kernel(const float* __restrict__ x, uint8_t* _
 #pragma unroll
     for (int u = 0; u < kEwU; ++u) {
       const long long e = base + 256ll * u;
-      if (e < n4)
-        bits[e] = (uint8_t)((v[u].x > 0.f ? 1 : 0) | (v[u].y > 0.f ? 2 : 0) | (v[u].z > 0.f ? 4 : 0) | (v[u].w > 0.f ? 8 : 0));
+      if (e < n4) bits[e] = hnd::relu_mask_nibble(v[u]);
     }
   }
 }

@@ -1,8 +1,9 @@
 // The stream-K "relay" of the B-streamed persistent GEMMs (conv_bstream.hip: fp32 MFMA, conv_bxs.hip: bf16x3 emulation):
 // the place the protocol is described and most of it lives -- the library's only synchronisation between workgroups.
-// Device side: relay_split, relay_load_head, relay_park_head.  Host side: the workspace size, the grid rule and the
-// launch-time check of the error word (defined in conv_bstream.hip).  Still written out in EACH kernel, and to be changed
-// in both together: the flag pointer, the epoch load, launch_done (ticket + launch counter) and seg_of (see below why).
+// Device side: relay_split, relay_load_head, relay_park_head and the load streams' position (RelayPos).  Host side: the
+// workspace size, the grid rule and the launch-time check of the error word (defined in conv_bstream.hip).  Still written out in EACH kernel, and to be changed
+// in both together: the flag pointer, the epoch load, launch_done (ticket + launch counter) and seg_of (see below why); the
+// two-line wrappers pos_init / pos_next over RelayPos sit beside seg_of.
 //
 // Work split (a stream-K that keeps the accumulation order): the launch is T tiles x `nit` iterations of 128 k;
 // workgroup w (numbered so that one XCD holds consecutive w) takes the units [U w / G, U (w+1) / G) of that linear
@@ -55,7 +56,9 @@ int relay_timeouts(int reset);
 // not a struct with state: bstream_kernel and bxs_kernel run at the register limit, and hipcc's allocation changed as soon
 // as the split went through an aggregate or spin_limit / err were copied at the top of the kernel (NOTEBOOK section 15).
 // With these signatures every instantiation compiles to the parent's instruction stream.  What stays in each kernel, a few
-// lines each and commented there: the flag pointer, the epoch load, launch_done and seg_of.
+// lines each and commented there: the flag pointer, the epoch load, launch_done and seg_of.  (launch_done as a shared
+// function over (relay, relay_f, G, epoch, tid) was tried and moved instructions in all 16 instantiations: NOTEBOOK
+// section 18.)
 // Fixed geometry, on both sides: workgroups of RELAY_THREADS threads, each parking its 4 x 4 f32x4 accumulators (a 128 x 128
 // or 256 x 64 tile) = RELAY_SET floats per workgroup.
 
@@ -78,6 +81,24 @@ __device__ __forceinline__ bool relay_split(const float* relay, int lb, int G, i
     if (lb >= T) return false;
     nfull = nseg = (T - lb + G - 1) / G;                // tiles lb, lb + G, ...
   }
+  return true;
+}
+
+// A load stream's position in the workgroup's segment list (seg_of: the kernel's own lambda)
+struct RelayPos { int seg, it, it1, tile; };
+template <class S>
+__device__ __forceinline__ void relay_pos_init(RelayPos& q, S& seg_of) {
+  int kind;
+  q.seg = 0;
+  seg_of(0, q.tile, q.it, q.it1, kind);
+}
+template <class S>
+__device__ __forceinline__ bool relay_pos_next(RelayPos& q, int nseg, S& seg_of) {      // true: entered a new segment
+  if (q.it + 1 < q.it1) { ++q.it; return false; }
+  if (q.seg + 1 >= nseg) return false;
+  int kind;
+  ++q.seg;
+  seg_of(q.seg, q.tile, q.it, q.it1, kind);
   return true;
 }
 
