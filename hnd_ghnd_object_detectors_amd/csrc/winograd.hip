@@ -1,15 +1,19 @@
-// Winograd F(2x2, 3x3) and F(4x4, 3x3) for the stride-1, pad-1 3x3 convolutions (frozen ResNet conv2, FPN output convs, and their
-// data gradients): Y = A^T [ (G g G^T) .* (B^T d B) ] A per 2x2 output tile, i.e. 16 multiplies per input/output
-// channel pair instead of 36.  The 16 element-wise products over channels are 16 independent GEMMs
+// Winograd minimal filtering for the stride-1 convolutions: F(2x2 | 4x4 | 6x6, 3x3) for the pad-1 3x3 convolutions (frozen
+// ResNet conv2, FPN output convs, and their data gradients) and F(4x4 | 6x6, 2x2) for the student head's 2x2 convolutions,
+// their data gradients and, in the Winograd domain, their weight gradients.  Y = A^T [ (G g G^T) .* (B^T d B) ] A per
+// T x T output tile, i.e. P^2 = (T + R - 1)^2 multiplies per input/output channel pair instead of (T R)^2.  The P^2
+// element-wise products over channels are P^2 independent GEMMs
 //     M_f [tiles x cout] = V_f [tiles x cin] * U_f^T [cin x cout]
-// which run as ONE launch of the implicit-GEMM kernel (conv_igemm.hip: a 1x1 "conv" over 16*tiles_pad pixels whose
-// weight matrix is selected per 128-row group).  This file holds the three HBM-bound transforms around it.
-// fp32 throughout; the transforms only add / halve, so the result differs from direct summation by ~1e-6 relative.
+// which run as ONE launch of the implicit-GEMM kernel (conv_igemm.hip: a 1x1 "conv" over P^2 * tiles_pad pixels whose
+// weight matrix is selected per 128-row group).  This file holds the HBM-bound transforms around it: one kernel per ROLE
+// (weights, input, output, dy, weight-gradient output), instantiated per scheme of winograd_schemes.h, which holds
+// everything that differs between the schemes.  fp32 throughout.
 #include <type_traits>
 
 #include "common.h"
+#include "winograd_schemes.h"
 
-using hnd::f32x4;
+using namespace wino;
 
 namespace {
 
@@ -22,55 +26,6 @@ inline int grid_for(long long work_items, int threads = 256) {
   return (int)b;
 }
 
-
-// U_f[co][ci] = (G g G^T)[f], g = w[co][ci] (forward) or w[ci][co] flipped (data gradient), written in the packed
-// GEMM-operand layout of hnd_pack_weights: [16][rows_pad][kdim], K (= input channel of the GEMM) contiguous.
-__global__ void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
-                                    int rows, int rows_pad, int kdim) {
-  // GEMM rows = output channels of this conv direction, K = its input channels
-  const long long total = (long long)rows_pad * kdim;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
-    const int r = hnd::chan_of_row(pr);
-    const int kreal = dgrad ? cout : cin;
-    float g[3][3];
-    const bool ok = r < rows && k < kreal;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        float v = 0.f;
-        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * 3 + (2 - i)) * 3 + (2 - j)]      // w[co=k][ci=r], flipped
-                          : w[(((size_t)r * cin + k) * 3 + i) * 3 + j];
-        g[i][j] = v;
-      }
-    float t[4][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      t[0][j] = g[0][j];
-      t[1][j] = 0.5f * (g[0][j] + g[1][j] + g[2][j]);
-      t[2][j] = 0.5f * (g[0][j] - g[1][j] + g[2][j]);
-      t[3][j] = g[2][j];
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float u0 = t[i][0], u1 = 0.5f * (t[i][0] + t[i][1] + t[i][2]), u2 = 0.5f * (t[i][0] - t[i][1] + t[i][2]),
-                  u3 = t[i][2];
-      float* dst = u + ((size_t)(i * 4) * rows_pad + pr) * kdim + k;
-      const size_t fs = (size_t)rows_pad * kdim;
-      dst[0] = u0; dst[fs] = u1; dst[2 * fs] = u2; dst[3 * fs] = u3;
-    }
-  }
-}
-
-struct WinoGeom {
-  int n, h, w, c;          // tensor being transformed (input: c = cin; output: c = ldc of y)
-  int th, tw;              // tiles per image
-  int tiles_pad;           // rows per component in V / M (multiple of 128)
-};
-
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // The transformed product M is read exactly once, by the output transform: nontemporal loads keep it from displacing the
 // output rows being written (round 4, in-step A/B: wino_output 3.61 -> 3.30 ms; nontemporal STORES of V gained nothing
 // in the step -- the GEMM that follows wants V where it is).
@@ -82,65 +37,192 @@ __device__ __forceinline__ void arrive(const f32x2& a, const f32x2& b) {
   asm volatile("" ::"v"(a.x), "v"(a.y), "v"(b.x), "v"(b.y));
 }
 
-// V[f][t][c] = (B^T d B)[f] of the 4x4 input patch of tile t (rows 2ty-1.., cols 2tx-1..), zero outside the image.
-// Optional prologue on in-bounds elements: a = x*scale[c] + shift[c], relu.
-__global__ void wino_input_kernel(const float* __restrict__ x, float* __restrict__ v, const WinoGeom g,
-                                  const float* __restrict__ pro_scale, const float* __restrict__ pro_shift,
-                                  int pro_relu) {
-  const int c4n = g.c >> 2;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c4n;
-  const size_t fs = (size_t)g.tiles_pad * g.c;           // component stride
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(e % c4n);
-    long long t = e / c4n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x4 ps = {1.f, 1.f, 1.f, 1.f}, pb = {0.f, 0.f, 0.f, 0.f};
-    if (pro_scale) {
-      ps = *(const f32x4*)(pro_scale + c4 * 4);
-      pb = *(const f32x4*)(pro_shift + c4 * 4);
+// ---------------------------------------------------------------------------------- the pieces every transform shares
+template <class V> constexpr int lanes_of = sizeof(V) / sizeof(float);
+
+template <class V> __device__ __forceinline__ V splat(float s);
+template <> __device__ __forceinline__ f32x2 splat<f32x2>(float s) { return f32x2{s, s}; }
+template <> __device__ __forceinline__ f32x4 splat<f32x4>(float s) { return f32x4{s, s, s, s}; }
+
+__device__ __forceinline__ f32x2 lanes_max(f32x2 a, float f) { a.x = fmaxf(a.x, f); a.y = fmaxf(a.y, f); return a; }
+__device__ __forceinline__ f32x4 lanes_max(f32x4 a, float f) {
+  a.x = fmaxf(a.x, f); a.y = fmaxf(a.y, f); a.z = fmaxf(a.z, f); a.w = fmaxf(a.w, f);
+  return a;
+}
+
+// first work item of a thread's grid-stride loop; XCD: blocks walk the items with hnd::xcd_contiguous_block()
+template <bool XCD>
+__device__ __forceinline__ long long first_item() {
+  if constexpr (XCD) return hnd::xcd_contiguous_block() * (long long)blockDim.x + threadIdx.x;
+  else return blockIdx.x * (long long)blockDim.x + threadIdx.x;
+}
+
+// work item e -> channel group c (fastest), tile t = (b, ty, tx)
+struct TileItem {
+  long long t;
+  int c, tx, ty, b;
+};
+__device__ __forceinline__ TileItem tile_item(long long e, int cn, int th, int tw) {
+  TileItem it;
+  it.c = (int)(e % cn);
+  it.t = e / cn;
+  it.tx = (int)(it.t % tw);
+  const long long q = it.t / tw;
+  it.ty = (int)(q % th);
+  it.b = (int)(q / th);
+  return it;
+}
+
+// Optional prologue on in-bounds elements of an input transform: a = x*scale[c] + shift[c], relu.
+template <class V>
+struct Prologue {
+  bool on;
+  V ps, pb;
+  float floor_;
+  __device__ __forceinline__ Prologue(const float* scale, const float* shift, int relu, int c)
+      : on(scale != nullptr), ps(splat<V>(1.f)), pb(splat<V>(0.f)), floor_(relu ? 0.f : -INFINITY) {
+    if (on) {
+      ps = *(const V*)(scale + c * lanes_of<V>);
+      pb = *(const V*)(shift + c * lanes_of<V>);
     }
-    const float floor_ = pro_relu ? 0.f : -INFINITY;
-    f32x4 d[4][4];
+  }
+  __device__ __forceinline__ V operator()(V a) const { return on ? lanes_max(a * ps + pb, floor_) : a; }
+};
+
+// d[j][i] (column j is one array) = f(x[b][y0 + i][x0 + j][c ...]), zero outside the h x w map
+template <int N, class V, class F>
+__device__ __forceinline__ void load_patch(V (&d)[N][N], const float* __restrict__ x, int b, int y0, int x0, int h, int w,
+                                           int ld, int coff, F f) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int iy = 2 * ty - 1 + i;
+  for (int i = 0; i < N; ++i) {
+    const int iy = y0 + i;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int ix = 2 * tx - 1 + j;
-        const bool ok = (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w;
-        const size_t off = ok ? (((size_t)b * g.h + iy) * g.w + ix) * g.c + c4 * 4 : 0;
-        f32x4 a = *(const f32x4*)(x + off);
-        if (pro_scale) {
-          a = a * ps + pb;
-          a.x = fmaxf(a.x, floor_); a.y = fmaxf(a.y, floor_); a.z = fmaxf(a.z, floor_); a.w = fmaxf(a.w, floor_);
-        }
-        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-        d[i][j] = ok ? a : z;
-      }
-    }
-    f32x4 r[4][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {          // B^T d
-      r[0][j] = d[0][j] - d[2][j];
-      r[1][j] = d[1][j] + d[2][j];
-      r[2][j] = d[2][j] - d[1][j];
-      r[3][j] = d[1][j] - d[3][j];
-    }
-    float* dst = v + (size_t)t * g.c + c4 * 4;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {          // (.) B
-      *(f32x4*)(dst + (size_t)(i * 4 + 0) * fs) = r[i][0] - r[i][2];
-      *(f32x4*)(dst + (size_t)(i * 4 + 1) * fs) = r[i][1] + r[i][2];
-      *(f32x4*)(dst + (size_t)(i * 4 + 2) * fs) = r[i][2] - r[i][1];
-      *(f32x4*)(dst + (size_t)(i * 4 + 3) * fs) = r[i][1] - r[i][3];
+    for (int j = 0; j < N; ++j) {
+      const int ix = x0 + j;
+      const bool ok = (unsigned)iy < (unsigned)h && (unsigned)ix < (unsigned)w;
+      const size_t off = ok ? (((size_t)b * h + iy) * w + ix) * ld + coff : 0;
+      const V a = f(off);
+      d[j][i] = ok ? a : splat<V>(0.f);
     }
   }
 }
 
+// dst[(i * PO + j) * fs] = (M d M^T)[i][j] for the row function `row` of M (PI -> PO): down the columns of d, then along
+// the rows, straight to memory
+template <int PI, int PO, class V, class Row>
+__device__ __forceinline__ void transform_store(const V (&d)[PI][PI], float* __restrict__ dst, size_t fs, Row row) {
+  V r[PO][PI];
+#pragma unroll
+  for (int j = 0; j < PI; ++j) {
+    V o[PO];
+    row(d[j], o);
+#pragma unroll
+    for (int i = 0; i < PO; ++i) r[i][j] = o[i];
+  }
+#pragma unroll
+  for (int i = 0; i < PO; ++i) {
+    V o[PO];
+    row(r[i], o);
+#pragma unroll
+    for (int j = 0; j < PO; ++j) *(V*)(dst + (size_t)(i * PO + j) * fs) = o[j];
+  }
+}
+
+// s[a][j] = (A^T m)[a][j] of the P x P GEMM results of a tile (nontemporal loads, down the columns)
+template <class S>
+__device__ __forceinline__ void load_at(const float* __restrict__ src, size_t fs, typename S::V (&s)[S::T][S::P]) {
+  using V = typename S::V;
+#pragma unroll
+  for (int j = 0; j < S::P; ++j) {
+    V col[S::P], o[S::T];
+#pragma unroll
+    for (int i = 0; i < S::P; ++i) col[i] = HND_NT_LOAD((const V*)(src + (size_t)(i * S::P + j) * fs));
+    S::at(col, o);
+#pragma unroll
+    for (int a = 0; a < S::T; ++a) s[a][j] = o[a];
+  }
+}
+
+// Per-block (s1, s2) per output channel -> stats[blockIdx][2][cout].  Threads tid and tid + k*cout/2 hold the same channel
+// pair (512 % cout == 0): fold them in a fixed order.
+__device__ __forceinline__ void block_stats_store(f32x2 s1, f32x2 s2, int cout, float* __restrict__ stats) {
+  __shared__ float red[2][512];
+  red[0][threadIdx.x * 2] = s1.x; red[0][threadIdx.x * 2 + 1] = s1.y;
+  red[1][threadIdx.x * 2] = s2.x; red[1][threadIdx.x * 2 + 1] = s2.y;
+  __syncthreads();
+  if ((int)threadIdx.x < cout) {
+    float a1 = 0.f, a2 = 0.f;
+    for (int k = threadIdx.x; k < 512; k += cout) { a1 += red[0][k]; a2 += red[1][k]; }
+    float* st = stats + (size_t)blockIdx.x * 2 * cout;
+    st[threadIdx.x] = a1;
+    st[cout + threadIdx.x] = a2;
+  }
+}
+
+// ---------------------------------------------------------------------------------- weights
+// U_f[co][ci] = (G g G^T)[f], g = w[co][ci] (forward) or w[ci][co] flipped (data gradient), written in the packed
+// GEMM-operand layout of hnd_pack_weights: [P*P][rows_pad][kdim], K (= input channel of the GEMM) contiguous.
+// GEMM rows = output channels of this conv direction, K = its input channels.
+template <class S>
+__global__ void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
+                                    int rows, int rows_pad, int kdim) {
+  constexpr int R = S::R, P = S::P;
+  const long long total = (long long)rows_pad * kdim;
+  const int kreal = dgrad ? cout : cin;
+  const size_t fs = (size_t)rows_pad * kdim;
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
+    const int r = hnd::chan_of_row(pr);
+    const bool ok = r < rows && k < kreal;
+    float g[R][R];                          // g[j][i]: column j of the filter
+#pragma unroll
+    for (int i = 0; i < R; ++i)
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        float v = 0.f;
+        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * R + (R - 1 - i)) * R + (R - 1 - j)]      // w[co=k][ci=r], flipped
+                          : w[(((size_t)r * cin + k) * R + i) * R + j];
+        g[j][i] = v;
+      }
+    float t[R][P];                          // t[j][i] = (G g)[i][j]
+#pragma unroll
+    for (int j = 0; j < R; ++j) S::g(g[j], t[j]);
+#pragma unroll
+    for (int i = 0; i < P; ++i) {
+      float row[R], o[P];
+#pragma unroll
+      for (int j = 0; j < R; ++j) row[j] = t[j][i];
+      S::g(row, o);
+      float* dst = u + ((size_t)(i * P) * rows_pad + pr) * kdim + k;
+#pragma unroll
+      for (int j = 0; j < P; ++j) dst[(size_t)j * fs] = o[j];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------- input
+// V[f][t][c] = (B^T d B)[f] of the P x P input patch of tile t (rows T ty - pad .., cols T tx - pad ..), zero outside the
+// image, after the optional prologue.
+template <class S>
+__global__ void __launch_bounds__(S::kLaunchBound)
+wino_input_kernel(const float* __restrict__ x, float* __restrict__ v, const typename S::Geom g,
+                  const float* __restrict__ pro_scale, const float* __restrict__ pro_shift, int pro_relu) {
+  using V = typename S::V;
+  constexpr int L = lanes_of<V>;
+  const int cn = g.c / L;
+  const long long total = (long long)g.n * g.th * g.tw * cn;
+  const size_t fs = (size_t)g.tiles_pad * g.c;           // component stride
+  for (long long e = first_item<S::kXcdWalk>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, cn, g.th, g.tw);
+    const Prologue<V> pro(pro_scale, pro_shift, pro_relu, it.c);
+    V d[S::P][S::P];
+    load_patch(d, x, it.b, S::T * it.ty - S::pad(g), S::T * it.tx - S::pad(g), g.h, g.w, g.c, it.c * L,
+               [&](size_t off) { return pro(*(const V*)(x + off)); });
+    transform_store<S::P, S::P>(d, v + (size_t)it.t * g.c + it.c * L, fs, [](const auto& in, auto& out) { S::bt(in, out); });
+  }
+}
+
+// ---------------------------------------------------------------------------------- 3x3 output
 struct WinoEpilogue {
   const float* epi_scale;
   const float* epi_shift;
@@ -160,240 +242,90 @@ __device__ __forceinline__ void wino_store_nibble(uint8_t* mask_out, size_t off,
 }
 
 // y[2ty+a][2tx+b][c] = epilogue( (A^T m A)[a][b] ), m = the 16 GEMM results of tile t; same epilogue order as the
-// implicit-GEMM kernel: scale/shift, + res1, mask (ReLU backward), ReLU.
+// implicit-GEMM kernel: scale/shift, + res1, mask (ReLU backward), ReLU.  F(2x2,3x3) keeps an output kernel of its own:
+// four channels per thread, epilogue operands read at run time, no mask_out and no interior path.
 __global__ void wino_output_kernel(const float* __restrict__ m, float* __restrict__ y, const WinoGeom g, int cout,
                                    const WinoEpilogue ep) {
+  using S = F23;
   const int c4n = (cout + 3) >> 2;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c4n;
+  const long long total = (long long)g.n * g.th * g.tw * c4n;
   const size_t fs = (size_t)g.tiles_pad * cout;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c4 = (int)(e % c4n);
-    long long t = e / c4n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    const float* src = m + (size_t)t * cout + c4 * 4;
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, c4n, g.th, g.tw);
+    const int c4 = it.c, tx = it.tx, ty = it.ty, b = it.b;
     f32x4 s[2][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {          // A^T m
-      const f32x4 m0 = HND_NT_LOAD((const f32x4*)(src + (size_t)(0 * 4 + j) * fs)), m1 = HND_NT_LOAD((const f32x4*)(src + (size_t)(1 * 4 + j) * fs)),
-                  m2 = HND_NT_LOAD((const f32x4*)(src + (size_t)(2 * 4 + j) * fs)), m3 = HND_NT_LOAD((const f32x4*)(src + (size_t)(3 * 4 + j) * fs));
-      s[0][j] = m0 + m1 + m2;
-      s[1][j] = m1 - m2 - m3;
-    }
+    load_at<S>(m + (size_t)it.t * cout + c4 * 4, fs, s);
     f32x4 es = {1.f, 1.f, 1.f, 1.f}, eb = {0.f, 0.f, 0.f, 0.f};
     if (ep.epi_scale) es = *(const f32x4*)(ep.epi_scale + c4 * 4);
     if (ep.epi_shift) eb = *(const f32x4*)(ep.epi_shift + c4 * 4);
 #pragma unroll
     for (int a = 0; a < 2; ++a) {
       const int oy = 2 * ty + a;
+      f32x4 o[2];
+      S::at(s[a], o);
 #pragma unroll
       for (int bb = 0; bb < 2; ++bb) {
         const int ox = 2 * tx + bb;
         if (oy >= g.h || ox >= g.w) continue;
-        f32x4 v = bb == 0 ? s[a][0] + s[a][1] + s[a][2] : s[a][1] - s[a][2] - s[a][3];
-        v = v * es + eb;
+        f32x4 v = o[bb] * es + eb;
         const size_t off = (((size_t)b * g.h + oy) * g.w + ox) * g.c + c4 * 4;
         if (ep.res1) v += *(const f32x4*)(ep.res1 + off);
         if (ep.mask) {
           const f32x4 k = *(const f32x4*)(ep.mask + off);
           v.x = k.x > 0.f ? v.x : 0.f; v.y = k.y > 0.f ? v.y : 0.f; v.z = k.z > 0.f ? v.z : 0.f; v.w = k.w > 0.f ? v.w : 0.f;
         }
-        if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (ep.relu) v = lanes_max(v, 0.f);
         *(f32x4*)(y + off) = v;
       }
     }
   }
 }
 
-
-// ================================================================================== F(4x4, 3x3)
-// Interpolation points {0, +-1, +-2, inf}: 36 products per 4x4 output tile = 4x fewer multiplies than direct, and
-// the transformed tensors inflate by 36/16 = 2.25x (F(2x2,3x3): 4x).  Two channels per thread keep the 6x6 patch
-// in 72 VGPRs.
-__global__ void wino4_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
-                                     int rows, int rows_pad, int kdim) {
-  const long long total = (long long)rows_pad * kdim;
-  const int kreal = dgrad ? cout : cin;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
-    const int r = hnd::chan_of_row(pr);
-    const bool ok = r < rows && k < kreal;
-    float g[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        float v = 0.f;
-        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * 3 + (2 - i)) * 3 + (2 - j)]
-                          : w[(((size_t)r * cin + k) * 3 + i) * 3 + j];
-        g[i][j] = v;
-      }
-    // G = [1/4 0 0; -1/6 -1/6 -1/6; -1/6 1/6 -1/6; 1/24 1/12 1/6; 1/24 -1/12 1/6; 0 0 1]
-    float t[6][3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float a = g[0][j], b = g[1][j], c = g[2][j];
-      t[0][j] = a * (1.f / 4.f);
-      t[1][j] = -(a + b + c) * (1.f / 6.f);
-      t[2][j] = (-a + b - c) * (1.f / 6.f);
-      t[3][j] = a * (1.f / 24.f) + b * (1.f / 12.f) + c * (1.f / 6.f);
-      t[4][j] = a * (1.f / 24.f) - b * (1.f / 12.f) + c * (1.f / 6.f);
-      t[5][j] = c;
-    }
-    const size_t fs = (size_t)rows_pad * kdim;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const float a = t[i][0], b = t[i][1], c = t[i][2];
-      float* dst = u + ((size_t)(i * 6) * rows_pad + pr) * kdim + k;
-      dst[0] = a * (1.f / 4.f);
-      dst[fs] = -(a + b + c) * (1.f / 6.f);
-      dst[2 * fs] = (-a + b - c) * (1.f / 6.f);
-      dst[3 * fs] = a * (1.f / 24.f) + b * (1.f / 12.f) + c * (1.f / 6.f);
-      dst[4 * fs] = a * (1.f / 24.f) - b * (1.f / 12.f) + c * (1.f / 6.f);
-      dst[5 * fs] = c;
-    }
-  }
-}
-
-// B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1] applied to 6 values
-#define HND_WINO4_BT(d0, d1, d2, d3, d4, d5, o0, o1, o2, o3, o4, o5) \
-  do {                                                               \
-    const f32x2 t0_ = 4.f * d0 - 5.f * d2 + d4;                      \
-    const f32x2 t1_ = -4.f * (d1 + d2) + d3 + d4;                    \
-    const f32x2 t2_ = 4.f * (d1 - d2) - d3 + d4;                     \
-    const f32x2 t3_ = -2.f * d1 - d2 + 2.f * d3 + d4;                \
-    const f32x2 t4_ = 2.f * d1 - d2 - 2.f * d3 + d4;                 \
-    const f32x2 t5_ = 4.f * d1 - 5.f * d3 + d5;                      \
-    o0 = t0_; o1 = t1_; o2 = t2_; o3 = t3_; o4 = t4_; o5 = t5_;      \
-  } while (0)
-
-__global__ void wino4_input_kernel(const float* __restrict__ x, float* __restrict__ v, const WinoGeom g,
-                                   const float* __restrict__ pro_scale, const float* __restrict__ pro_shift,
-                                   int pro_relu) {
-  const int c2n = g.c >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * g.c;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 ps = {1.f, 1.f}, pb = {0.f, 0.f};
-    if (pro_scale) {
-      ps = *(const f32x2*)(pro_scale + c2 * 2);
-      pb = *(const f32x2*)(pro_shift + c2 * 2);
-    }
-    const float floor_ = pro_relu ? 0.f : -INFINITY;
-    f32x2 d[6][6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int iy = 4 * ty - 1 + i;
-#pragma unroll
-      for (int j = 0; j < 6; ++j) {
-        const int ix = 4 * tx - 1 + j;
-        const bool ok = (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w;
-        const size_t off = ok ? (((size_t)b * g.h + iy) * g.w + ix) * g.c + c2 * 2 : 0;
-        f32x2 a = *(const f32x2*)(x + off);
-        if (pro_scale) {
-          a = a * ps + pb;
-          a.x = fmaxf(a.x, floor_); a.y = fmaxf(a.y, floor_);
-        }
-        const f32x2 z = {0.f, 0.f};
-        d[i][j] = ok ? a : z;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 6; ++j)            // B^T d (down the columns, in place)
-      HND_WINO4_BT(d[0][j], d[1][j], d[2][j], d[3][j], d[4][j], d[5][j], d[0][j], d[1][j], d[2][j], d[3][j], d[4][j],
-                   d[5][j]);
-    float* dst = v + (size_t)t * g.c + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {          // (.) B (along the rows), straight to memory
-      f32x2 o0, o1, o2, o3, o4, o5;
-      HND_WINO4_BT(d[i][0], d[i][1], d[i][2], d[i][3], d[i][4], d[i][5], o0, o1, o2, o3, o4, o5);
-      *(f32x2*)(dst + (size_t)(i * 6 + 0) * fs) = o0;
-      *(f32x2*)(dst + (size_t)(i * 6 + 1) * fs) = o1;
-      *(f32x2*)(dst + (size_t)(i * 6 + 2) * fs) = o2;
-      *(f32x2*)(dst + (size_t)(i * 6 + 3) * fs) = o3;
-      *(f32x2*)(dst + (size_t)(i * 6 + 4) * fs) = o4;
-      *(f32x2*)(dst + (size_t)(i * 6 + 5) * fs) = o5;
-    }
-  }
-}
-
-// A^T = [1 1 1 1 1 0; 0 1 -1 2 -2 0; 0 1 1 4 4 0; 0 1 -1 8 -8 1] applied to 6 values
-#define HND_WINO4_AT(m0, m1, m2, m3, m4, m5, o0, o1, o2, o3) \
-  do {                                                       \
-    const f32x2 p12 = m1 + m2, q12 = m1 - m2, p34 = m3 + m4, q34 = m3 - m4; \
-    o0 = m0 + p12 + p34;                                     \
-    o1 = q12 + 2.f * q34;                                    \
-    o2 = p12 + 4.f * p34;                                    \
-    o3 = q12 + 8.f * q34 + m5;                               \
-  } while (0)
-
-// The epilogue operands are template parameters and tiles that lie inside the map take a branch-free path: with
-// run-time `if (ptr)` operands or per-output bounds branches hipcc puts `s_waitcnt vmcnt(0)` in front of every store
-// (stores count in vmcnt on gfx9), which serialises the 16 / 36 stores of a tile.
-template <bool RES, bool MASK>
-__global__ void wino4_output_kernel(const float* __restrict__ m, float* __restrict__ y, const WinoGeom g, int cout,
-                                    const WinoEpilogue ep) {
+// F(4x4,3x3) / F(6x6,3x3).  The epilogue operands are template parameters and tiles that lie inside the map take a
+// branch-free path: with run-time `if (ptr)` operands or per-output bounds branches hipcc puts `s_waitcnt vmcnt(0)` in
+// front of every store (stores count in vmcnt on gfx9), which serialises the 16 / 36 stores of a tile.
+template <class S, bool RES, bool MASK>
+__global__ void __launch_bounds__(S::kLaunchBound)
+wino3_output_kernel(const float* __restrict__ m, float* __restrict__ y, const WinoGeom g, int cout, const WinoEpilogue ep) {
+  constexpr int T = S::T;
   const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
+  const long long total = (long long)g.n * g.th * g.tw * c2n;
   const size_t fs = (size_t)g.tiles_pad * cout;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    const float* src = m + (size_t)t * cout + c2 * 2;
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, c2n, g.th, g.tw);
+    const int c2 = it.c, tx = it.tx, ty = it.ty, b = it.b;
     f32x2 es = {1.f, 1.f}, eb = {0.f, 0.f};
     if (ep.epi_scale) es = *(const f32x2*)(ep.epi_scale + c2 * 2);
     if (ep.epi_shift) eb = *(const f32x2*)(ep.epi_shift + c2 * 2);
-    f32x2 s[4][6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {          // A^T m (down the columns)
-      const f32x2 m0 = HND_NT_LOAD((const f32x2*)(src + (size_t)(0 * 6 + j) * fs)), m1 = HND_NT_LOAD((const f32x2*)(src + (size_t)(1 * 6 + j) * fs)),
-                  m2 = HND_NT_LOAD((const f32x2*)(src + (size_t)(2 * 6 + j) * fs)), m3 = HND_NT_LOAD((const f32x2*)(src + (size_t)(3 * 6 + j) * fs)),
-                  m4 = HND_NT_LOAD((const f32x2*)(src + (size_t)(4 * 6 + j) * fs)), m5 = HND_NT_LOAD((const f32x2*)(src + (size_t)(5 * 6 + j) * fs));
-      HND_WINO4_AT(m0, m1, m2, m3, m4, m5, s[0][j], s[1][j], s[2][j], s[3][j]);
-    }
+    f32x2 s[T][S::P];
+    load_at<S>(m + (size_t)it.t * cout + c2 * 2, fs, s);
     arrive(es, eb);
     auto emit = [&](auto checked) {
       constexpr bool CHK = decltype(checked)::value;
       // interior tiles: the residual / mask rows are fetched one output row ahead of the stores that use them
-      f32x2 rn[4], kn[4];
+      f32x2 rn[T], kn[T];
       auto fetch = [&](int a) {
-        const size_t row = (((size_t)b * g.h + 4 * ty + a) * g.w + 4 * tx) * g.c + c2 * 2;
+        const size_t row = (((size_t)b * g.h + T * ty + a) * g.w + T * tx) * g.c + c2 * 2;
 #pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
+        for (int bb = 0; bb < T; ++bb) {
           if (RES) rn[bb] = *(const f32x2*)(ep.res1 + row + (size_t)bb * g.c);
           if (MASK) kn[bb] = *(const f32x2*)(ep.mask + row + (size_t)bb * g.c);
         }
       };
       if (!CHK && (RES || MASK)) fetch(0);
 #pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int oy = 4 * ty + a;
-        f32x2 o[4], rc[4], kc[4];
-        HND_WINO4_AT(s[a][0], s[a][1], s[a][2], s[a][3], s[a][4], s[a][5], o[0], o[1], o[2], o[3]);
+      for (int a = 0; a < T; ++a) {
+        const int oy = T * ty + a;
+        f32x2 o[T], rc[T], kc[T];
+        S::at(s[a], o);
         if (!CHK && (RES || MASK)) {
 #pragma unroll
-          for (int bb = 0; bb < 4; ++bb) { rc[bb] = rn[bb]; kc[bb] = kn[bb]; }
-          if (a + 1 < 4) fetch(a + 1);
+          for (int bb = 0; bb < T; ++bb) { rc[bb] = rn[bb]; kc[bb] = kn[bb]; }
+          if (a + 1 < T) fetch(a + 1);
         }
 #pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int ox = 4 * tx + bb;
+        for (int bb = 0; bb < T; ++bb) {
+          const int ox = T * tx + bb;
           if (CHK && (oy >= g.h || ox >= g.w)) continue;
           f32x2 v = o[bb] * es + eb;
           const size_t off = (((size_t)b * g.h + oy) * g.w + ox) * g.c + c2 * 2;
@@ -403,662 +335,18 @@ __global__ void wino4_output_kernel(const float* __restrict__ m, float* __restri
           }
           if (RES) v += rc[bb];
           if (MASK) { v.x = kc[bb].x > 0.f ? v.x : 0.f; v.y = kc[bb].y > 0.f ? v.y : 0.f; }
-          if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
+          if (ep.relu) v = lanes_max(v, 0.f);
           *(f32x2*)(y + off) = v;
           if (ep.mask_out) wino_store_nibble(ep.mask_out, off, c2, v);
         }
       }
     };
-    if (4 * ty + 4 <= g.h && 4 * tx + 4 <= g.w) emit(std::false_type{});
+    if (T * ty + T <= g.h && T * tx + T <= g.w) emit(std::false_type{});
     else emit(std::true_type{});
   }
 }
 
-
-// ================================================================================== F(6x6, 3x3)
-// Interpolation points {0, +-1, +-2, +-1/2, inf}: 64 products per 6x6 output tile = 5.06x fewer multiplies than direct
-// (F(4x4,3x3): 4x) and transformed tensors of 64/36 = 1.78x the activation (F(4x4,3x3): 2.25x) -- 21 % fewer GEMM
-// flops AND 21 % fewer transform bytes than F(4x4,3x3).  fp32 error against exact convolution on post-ReLU data,
-// K = 256: rel-L2 5e-6 (F(4x4,3x3): 2.6e-6; direct fp32 summation: 2e-7) -- far inside the 1e-3 parity bar.  Used
-// where the 6x6 tiling wastes little (>= 50x84 maps); matrices (Cook-Toom, checked against direct correlation in
-// fp64 to 3e-14):
-//   B^T = [1 0 -21/4 0 21/4 0 -1 0; 0 1 1 -17/4 -17/4 1 1 0; 0 -1 1 17/4 -17/4 -1 1 0; 0 1/2 1/4 -5/2 -5/4 2 1 0;
-//          0 -1/2 1/4 5/2 -5/4 -2 1 0; 0 2 4 -5/2 -5 1/2 1 0; 0 -2 4 5/2 -5 -1/2 1 0; 0 -1 0 21/4 0 -21/4 0 1]
-//   G   = [1 0 0; -2/9 -2/9 -2/9; -2/9 2/9 -2/9; 1/90 1/45 2/45; 1/90 -1/45 2/45; 32/45 16/45 8/45;
-//          32/45 -16/45 8/45; 0 0 1]
-//   A^T = [1 1 1 1 1 1 1 0; 0 1 -1 2 -2 1/2 -1/2 0; 0 1 1 4 4 1/4 1/4 0; 0 1 -1 8 -8 1/8 -1/8 0;
-//          0 1 1 16 16 1/16 1/16 0; 0 1 -1 32 -32 1/32 -1/32 1]
-#define HND_WINO6_G(a, b, c, o)                                          \
-  do {                                                                   \
-    o[0] = a;                                                            \
-    o[1] = -(a + b + c) * (2.f / 9.f);                                   \
-    o[2] = (-a + b - c) * (2.f / 9.f);                                   \
-    o[3] = a * (1.f / 90.f) + b * (1.f / 45.f) + c * (2.f / 45.f);       \
-    o[4] = a * (1.f / 90.f) - b * (1.f / 45.f) + c * (2.f / 45.f);       \
-    o[5] = a * (32.f / 45.f) + b * (16.f / 45.f) + c * (8.f / 45.f);     \
-    o[6] = a * (32.f / 45.f) - b * (16.f / 45.f) + c * (8.f / 45.f);     \
-    o[7] = c;                                                            \
-  } while (0)
-
-__global__ void wino6_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
-                                     int rows, int rows_pad, int kdim) {
-  const long long total = (long long)rows_pad * kdim;
-  const int kreal = dgrad ? cout : cin;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
-    const int r = hnd::chan_of_row(pr);
-    const bool ok = r < rows && k < kreal;
-    float g[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int j = 0; j < 3; ++j) {
-        float v = 0.f;
-        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * 3 + (2 - i)) * 3 + (2 - j)]
-                          : w[(((size_t)r * cin + k) * 3 + i) * 3 + j];
-        g[i][j] = v;
-      }
-    float t[3][8];                          // t[j][i] = (G g)[i][j]
-#pragma unroll
-    for (int j = 0; j < 3; ++j) HND_WINO6_G(g[0][j], g[1][j], g[2][j], t[j]);
-    const size_t fs = (size_t)rows_pad * kdim;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      float o[8];
-      HND_WINO6_G(t[0][i], t[1][i], t[2][i], o);
-      float* dst = u + ((size_t)(i * 8) * rows_pad + pr) * kdim + k;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) dst[(size_t)j * fs] = o[j];
-    }
-  }
-}
-
-#define HND_WINO6_BT(d0, d1, d2, d3, d4, d5, d6, d7, o0, o1, o2, o3, o4, o5, o6, o7) \
-  do {                                                                               \
-    const f32x2 e26_ = d2 + d6 - 4.25f * d4, o15_ = d1 + d5 - 4.25f * d3;            \
-    const f32x2 e3_ = 0.25f * d2 - 1.25f * d4 + d6, o3_ = 0.5f * d1 - 2.5f * d3 + 2.f * d5; \
-    const f32x2 e5_ = 4.f * d2 - 5.f * d4 + d6, o5_ = 2.f * d1 - 2.5f * d3 + 0.5f * d5;     \
-    const f32x2 t0_ = d0 - d6 + 5.25f * (d4 - d2), t7_ = d7 - d1 + 5.25f * (d3 - d5);       \
-    o0 = t0_; o1 = e26_ + o15_; o2 = e26_ - o15_; o3 = e3_ + o3_; o4 = e3_ - o3_;     \
-    o5 = e5_ + o5_; o6 = e5_ - o5_; o7 = t7_;                                         \
-  } while (0)
-
-// 8x8 input patch of tile t (rows 6ty-1.., cols 6tx-1..), two channels per thread: 128 VGPRs of patch
-__global__ void __launch_bounds__(256) wino6_input_kernel(const float* __restrict__ x, float* __restrict__ v,
-                                                          const WinoGeom g, const float* __restrict__ pro_scale,
-                                                          const float* __restrict__ pro_shift, int pro_relu) {
-  const int c2n = g.c >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * g.c;
-  for (long long e = hnd::xcd_contiguous_block() * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 ps = {1.f, 1.f}, pb = {0.f, 0.f};
-    if (pro_scale) {
-      ps = *(const f32x2*)(pro_scale + c2 * 2);
-      pb = *(const f32x2*)(pro_shift + c2 * 2);
-    }
-    const float floor_ = pro_relu ? 0.f : -INFINITY;
-    f32x2 d[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int iy = 6 * ty - 1 + i;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int ix = 6 * tx - 1 + j;
-        const bool ok = (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w;
-        const size_t off = ok ? (((size_t)b * g.h + iy) * g.w + ix) * g.c + c2 * 2 : 0;
-        f32x2 a = *(const f32x2*)(x + off);
-        if (pro_scale) {
-          a = a * ps + pb;
-          a.x = fmaxf(a.x, floor_); a.y = fmaxf(a.y, floor_);
-        }
-        const f32x2 z = {0.f, 0.f};
-        d[i][j] = ok ? a : z;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j)            // B^T d (down the columns, in place)
-      HND_WINO6_BT(d[0][j], d[1][j], d[2][j], d[3][j], d[4][j], d[5][j], d[6][j], d[7][j], d[0][j], d[1][j], d[2][j],
-                   d[3][j], d[4][j], d[5][j], d[6][j], d[7][j]);
-    float* dst = v + (size_t)t * g.c + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {          // (.) B (along the rows), straight to memory
-      f32x2 o[8];
-      HND_WINO6_BT(d[i][0], d[i][1], d[i][2], d[i][3], d[i][4], d[i][5], d[i][6], d[i][7], o[0], o[1], o[2], o[3], o[4],
-                   o[5], o[6], o[7]);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) *(f32x2*)(dst + (size_t)(i * 8 + j) * fs) = o[j];
-    }
-  }
-}
-
-#define HND_WINO6_AT(m0, m1, m2, m3, m4, m5, m6, m7, o0, o1, o2, o3, o4, o5)            \
-  do {                                                                                  \
-    const f32x2 p12 = m1 + m2, q12 = m1 - m2, p34 = m3 + m4, q34 = m3 - m4, p56 = m5 + m6, q56 = m5 - m6; \
-    o0 = m0 + p12 + p34 + p56;                                                          \
-    o1 = q12 + 2.f * q34 + 0.5f * q56;                                                  \
-    o2 = p12 + 4.f * p34 + 0.25f * p56;                                                 \
-    o3 = q12 + 8.f * q34 + 0.125f * q56;                                                \
-    o4 = p12 + 16.f * p34 + 0.0625f * p56;                                              \
-    o5 = q12 + 32.f * q34 + 0.03125f * q56 + m7;                                        \
-  } while (0)
-
-template <bool RES, bool MASK>
-__global__ void __launch_bounds__(256) wino6_output_kernel(const float* __restrict__ m, float* __restrict__ y,
-                                                           const WinoGeom g, int cout, const WinoEpilogue ep) {
-  const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * cout;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    const float* src = m + (size_t)t * cout + c2 * 2;
-    f32x2 es = {1.f, 1.f}, eb = {0.f, 0.f};
-    if (ep.epi_scale) es = *(const f32x2*)(ep.epi_scale + c2 * 2);
-    if (ep.epi_shift) eb = *(const f32x2*)(ep.epi_shift + c2 * 2);
-    f32x2 s[6][8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {          // A^T m (down the columns)
-      f32x2 mm[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) mm[i] = HND_NT_LOAD((const f32x2*)(src + (size_t)(i * 8 + j) * fs));
-      HND_WINO6_AT(mm[0], mm[1], mm[2], mm[3], mm[4], mm[5], mm[6], mm[7], s[0][j], s[1][j], s[2][j], s[3][j], s[4][j],
-                   s[5][j]);
-    }
-    arrive(es, eb);
-    auto emit = [&](auto checked) {
-      constexpr bool CHK = decltype(checked)::value;
-      // interior tiles: the residual / mask rows are fetched one output row ahead of the stores that use them
-      f32x2 rn[6], kn[6];
-      auto fetch = [&](int a) {
-        const size_t row = (((size_t)b * g.h + 6 * ty + a) * g.w + 6 * tx) * g.c + c2 * 2;
-#pragma unroll
-        for (int bb = 0; bb < 6; ++bb) {
-          if (RES) rn[bb] = *(const f32x2*)(ep.res1 + row + (size_t)bb * g.c);
-          if (MASK) kn[bb] = *(const f32x2*)(ep.mask + row + (size_t)bb * g.c);
-        }
-      };
-      if (!CHK && (RES || MASK)) fetch(0);
-#pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const int oy = 6 * ty + a;
-        f32x2 o[6], rc[6], kc[6];
-        HND_WINO6_AT(s[a][0], s[a][1], s[a][2], s[a][3], s[a][4], s[a][5], s[a][6], s[a][7], o[0], o[1], o[2], o[3],
-                     o[4], o[5]);
-        if (!CHK && (RES || MASK)) {
-#pragma unroll
-          for (int bb = 0; bb < 6; ++bb) { rc[bb] = rn[bb]; kc[bb] = kn[bb]; }
-          if (a + 1 < 6) fetch(a + 1);
-        }
-#pragma unroll
-        for (int bb = 0; bb < 6; ++bb) {
-          const int ox = 6 * tx + bb;
-          if (CHK && (oy >= g.h || ox >= g.w)) continue;
-          f32x2 v = o[bb] * es + eb;
-          const size_t off = (((size_t)b * g.h + oy) * g.w + ox) * g.c + c2 * 2;
-          if (CHK) {
-            if (RES) rc[bb] = *(const f32x2*)(ep.res1 + off);
-            if (MASK) kc[bb] = *(const f32x2*)(ep.mask + off);
-          }
-          if (RES) v += rc[bb];
-          if (MASK) { v.x = kc[bb].x > 0.f ? v.x : 0.f; v.y = kc[bb].y > 0.f ? v.y : 0.f; }
-          if (ep.relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
-          *(f32x2*)(y + off) = v;
-          if (ep.mask_out) wino_store_nibble(ep.mask_out, off, c2, v);
-        }
-      }
-    };
-    if (6 * ty + 6 <= g.h && 6 * tx + 6 <= g.w) emit(std::false_type{});
-    else emit(std::true_type{});
-  }
-}
-
-
-// ================================================================================== F(4x4, 2x2)
-// The student head's 2x2 convolutions (src/models/mimic/resnet_layer.py:43-62) and their data gradients: points
-// {0, 1, -1, 2, inf}, 25 products per 4x4 output tile instead of 64 (2.56x fewer), transformed tensors 25/16 = 1.56x.
-//   A^T = [1 1 1 1 0; 0 1 -1 2 0; 0 1 1 4 0; 0 1 -1 8 1]
-//   G   = [1/2 0; -1/2 -1/2; -1/6 1/6; 1/6 1/3; 0 1]
-//   B^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1]
-// Correlation with padding q in {0, 1}: out[y][x] = sum_ij w[i][j] in[y+i-q][x+j-q], output (h+2q-1) x (w+2q-1).
-// The data gradient of such a conv is the same correlation with flipped, transposed weights and padding 1-q.
-__global__ void wino2_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
-                                     int rows, int rows_pad, int kdim) {
-  const long long total = (long long)rows_pad * kdim;
-  const int kreal = dgrad ? cout : cin;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
-    const int r = hnd::chan_of_row(pr);
-    const bool ok = r < rows && k < kreal;
-    float g[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float v = 0.f;
-        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * 2 + (1 - i)) * 2 + (1 - j)]
-                          : w[(((size_t)r * cin + k) * 2 + i) * 2 + j];
-        g[i][j] = v;
-      }
-    float t[5][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float a = g[0][j], b = g[1][j];
-      t[0][j] = 0.5f * a;
-      t[1][j] = -0.5f * (a + b);
-      t[2][j] = (b - a) * (1.f / 6.f);
-      t[3][j] = a * (1.f / 6.f) + b * (1.f / 3.f);
-      t[4][j] = b;
-    }
-    const size_t fs = (size_t)rows_pad * kdim;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const float a = t[i][0], b = t[i][1];
-      float* dst = u + ((size_t)(i * 5) * rows_pad + pr) * kdim + k;
-      dst[0] = 0.5f * a;
-      dst[fs] = -0.5f * (a + b);
-      dst[2 * fs] = (b - a) * (1.f / 6.f);
-      dst[3 * fs] = a * (1.f / 6.f) + b * (1.f / 3.f);
-      dst[4 * fs] = b;
-    }
-  }
-}
-
-#define HND_WINO2_BT(d0, d1, d2, d3, d4, o0, o1, o2, o3, o4) \
-  do {                                                       \
-    const f32x2 t0_ = 2.f * (d0 - d2) - d1 + d3;             \
-    const f32x2 t1_ = -2.f * d1 - d2 + d3;                   \
-    const f32x2 t2_ = 2.f * d1 - 3.f * d2 + d3;              \
-    const f32x2 t3_ = d3 - d1;                               \
-    const f32x2 t4_ = 2.f * (d1 - d3) - d2 + d4;             \
-    o0 = t0_; o1 = t1_; o2 = t2_; o3 = t3_; o4 = t4_;        \
-  } while (0)
-
-struct Wino2Geom {
-  int n, h, w, c;          // input tensor
-  int oh, ow;              // output extent (h + 2q - 1)
-  int th, tw, tiles_pad, pad;
-};
-
-__global__ void wino2_input_kernel(const float* __restrict__ x, float* __restrict__ v, const Wino2Geom g,
-                                   const float* __restrict__ pro_scale, const float* __restrict__ pro_shift,
-                                   int pro_relu) {
-  const int c2n = g.c >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * g.c;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 ps = {1.f, 1.f}, pb = {0.f, 0.f};
-    if (pro_scale) {
-      ps = *(const f32x2*)(pro_scale + c2 * 2);
-      pb = *(const f32x2*)(pro_shift + c2 * 2);
-    }
-    const float floor_ = pro_relu ? 0.f : -INFINITY;
-    f32x2 d[5][5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      const int iy = 4 * ty - g.pad + i;
-#pragma unroll
-      for (int j = 0; j < 5; ++j) {
-        const int ix = 4 * tx - g.pad + j;
-        const bool ok = (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w;
-        const size_t off = ok ? (((size_t)b * g.h + iy) * g.w + ix) * g.c + c2 * 2 : 0;
-        f32x2 a = *(const f32x2*)(x + off);
-        if (pro_scale) {
-          a = a * ps + pb;
-          a.x = fmaxf(a.x, floor_); a.y = fmaxf(a.y, floor_);
-        }
-        const f32x2 z = {0.f, 0.f};
-        d[i][j] = ok ? a : z;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 5; ++j)
-      HND_WINO2_BT(d[0][j], d[1][j], d[2][j], d[3][j], d[4][j], d[0][j], d[1][j], d[2][j], d[3][j], d[4][j]);
-    float* dst = v + (size_t)t * g.c + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      f32x2 o0, o1, o2, o3, o4;
-      HND_WINO2_BT(d[i][0], d[i][1], d[i][2], d[i][3], d[i][4], o0, o1, o2, o3, o4);
-      *(f32x2*)(dst + (size_t)(i * 5 + 0) * fs) = o0;
-      *(f32x2*)(dst + (size_t)(i * 5 + 1) * fs) = o1;
-      *(f32x2*)(dst + (size_t)(i * 5 + 2) * fs) = o2;
-      *(f32x2*)(dst + (size_t)(i * 5 + 3) * fs) = o3;
-      *(f32x2*)(dst + (size_t)(i * 5 + 4) * fs) = o4;
-    }
-  }
-}
-
-#define HND_WINO2_AT(m0, m1, m2, m3, m4, o0, o1, o2, o3) \
-  do {                                                   \
-    const f32x2 p12 = m1 + m2, q12 = m1 - m2;            \
-    o0 = m0 + p12 + m3;                                  \
-    o1 = q12 + 2.f * m3;                                 \
-    o2 = p12 + 4.f * m3;                                 \
-    o3 = q12 + 8.f * m3 + m4;                            \
-  } while (0)
-
-// Output transform (+ scale/shift, ReLU) of the 2x2 Winograd conv.  With `stats`, every block also writes the partial
-// (sum v, sum v^2) per output channel of the values it stored -> stats[blockIdx][2][cout]: the train-mode BatchNorm
-// statistics hnd_bn_finalize consumes (ntiles = gridDim.x).  Requires 512 % cout == 0 so a thread keeps its channels.
-__global__ void wino2_output_kernel(const float* __restrict__ m, float* __restrict__ y, const Wino2Geom g, int cout,
-                                    int ldc, const float* __restrict__ epi_scale, const float* __restrict__ epi_shift,
-                                    int relu, float* __restrict__ stats) {
-  __shared__ float red[2][512];
-  const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * cout;
-  f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    const float* src = m + (size_t)t * cout + c2 * 2;
-    f32x2 s[4][5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const f32x2 m0 = HND_NT_LOAD((const f32x2*)(src + (size_t)(0 * 5 + j) * fs)), m1 = HND_NT_LOAD((const f32x2*)(src + (size_t)(1 * 5 + j) * fs)),
-                  m2 = HND_NT_LOAD((const f32x2*)(src + (size_t)(2 * 5 + j) * fs)), m3 = HND_NT_LOAD((const f32x2*)(src + (size_t)(3 * 5 + j) * fs)),
-                  m4 = HND_NT_LOAD((const f32x2*)(src + (size_t)(4 * 5 + j) * fs));
-      HND_WINO2_AT(m0, m1, m2, m3, m4, s[0][j], s[1][j], s[2][j], s[3][j]);
-    }
-    f32x2 es = {1.f, 1.f}, eb = {0.f, 0.f};
-    if (epi_scale) es = *(const f32x2*)(epi_scale + c2 * 2);
-    if (epi_shift) eb = *(const f32x2*)(epi_shift + c2 * 2);
-    arrive(es, eb);
-    auto emit = [&](auto checked) {         // see wino4_output_kernel: interior tiles store without branches
-      constexpr bool CHK = decltype(checked)::value;
-#pragma unroll
-      for (int a = 0; a < 4; ++a) {
-        const int oy = 4 * ty + a;
-        f32x2 o[4];
-        HND_WINO2_AT(s[a][0], s[a][1], s[a][2], s[a][3], s[a][4], o[0], o[1], o[2], o[3]);
-#pragma unroll
-        for (int bb = 0; bb < 4; ++bb) {
-          const int ox = 4 * tx + bb;
-          if (CHK && (oy >= g.oh || ox >= g.ow)) continue;
-          f32x2 v = o[bb] * es + eb;
-          if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
-          *(f32x2*)(y + (((size_t)b * g.oh + oy) * g.ow + ox) * ldc + c2 * 2) = v;
-          s1 += v;
-          s2 += v * v;
-        }
-      }
-    };
-    if (4 * ty + 4 <= g.oh && 4 * tx + 4 <= g.ow) emit(std::false_type{});
-    else emit(std::true_type{});
-  }
-  if (stats) {
-    // threads tid and tid + k*c2n hold the same channel pair: fold them in a fixed order
-    red[0][threadIdx.x * 2] = s1.x; red[0][threadIdx.x * 2 + 1] = s1.y;
-    red[1][threadIdx.x * 2] = s2.x; red[1][threadIdx.x * 2 + 1] = s2.y;
-    __syncthreads();
-    if ((int)threadIdx.x < cout) {
-      float a1 = 0.f, a2 = 0.f;
-      for (int k = threadIdx.x; k < 512; k += cout) { a1 += red[0][k]; a2 += red[1][k]; }
-      float* st = stats + (size_t)blockIdx.x * 2 * cout;
-      st[threadIdx.x] = a1;
-      st[cout + threadIdx.x] = a2;
-    }
-  }
-}
-
-
-// ---------------------------------------------------------------------------------- F(2x2 taps, 4x4 tile): weight gradient
-// dW[i][j] = sum over tiles of sum_ab dy_t[a][b] d_t[a+i][b+j] is the minimal-filtering problem F(2x2, 4x4) with the
-// dy tile in the role of the filter.  Same points {0, 1, -1, 2, inf} => the data transform B^T d B is the V the
-// forward pass already produced; this kernel makes Z = G' dy_t G'^T,
-//   G' = [1/2 0 0 0; -1/2 -1/2 -1/2 -1/2; -1/6 1/6 -1/6 1/6; 1/6 1/3 2/3 4/3; 0 0 0 1],
-// 25 grouped GEMMs reduce S_f[co][ci] = sum_t Z_f[t][co] V_f[t][ci] over the tiles, and
-// dW = A'^T S A', A'^T = [1 1 1 1 0; 0 1 -1 2 1], is a per-(co, ci) epilogue.
-#define HND_WINO2_GP(g0, g1, g2, g3, o0, o1, o2, o3, o4)                                   \
-  do {                                                                                     \
-    const f32x2 e_ = g0 + g2, f_ = g1 + g3;                                                \
-    o0 = 0.5f * g0;                                                                        \
-    o1 = -0.5f * (e_ + f_);                                                                \
-    o2 = (f_ - e_) * (1.f / 6.f);                                                          \
-    o3 = g0 * (1.f / 6.f) + g1 * (1.f / 3.f) + g2 * (2.f / 3.f) + g3 * (4.f / 3.f);        \
-    o4 = g3;                                                                               \
-  } while (0)
-
-__global__ void wino2_dy_kernel(const float* __restrict__ dy, float* __restrict__ z, const Wino2Geom g, int cout,
-                                int ldy) {
-  const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * cout;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 d[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const int oy = 4 * ty + a;
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const int ox = 4 * tx + bb;
-        const bool ok = oy < g.oh && ox < g.ow;
-        const size_t off = ok ? (((size_t)b * g.oh + oy) * g.ow + ox) * ldy + c2 * 2 : 0;
-        const f32x2 v = *(const f32x2*)(dy + off);
-        const f32x2 zz = {0.f, 0.f};
-        d[a][bb] = ok ? v : zz;
-      }
-    }
-    f32x2 r[5][4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) HND_WINO2_GP(d[0][j], d[1][j], d[2][j], d[3][j], r[0][j], r[1][j], r[2][j], r[3][j], r[4][j]);
-    float* dst = z + (size_t)t * cout + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-      f32x2 o0, o1, o2, o3, o4;
-      HND_WINO2_GP(r[i][0], r[i][1], r[i][2], r[i][3], o0, o1, o2, o3, o4);
-      *(f32x2*)(dst + (size_t)(i * 5 + 0) * fs) = o0;
-      *(f32x2*)(dst + (size_t)(i * 5 + 1) * fs) = o1;
-      *(f32x2*)(dst + (size_t)(i * 5 + 2) * fs) = o2;
-      *(f32x2*)(dst + (size_t)(i * 5 + 3) * fs) = o3;
-      *(f32x2*)(dst + (size_t)(i * 5 + 4) * fs) = o4;
-    }
-  }
-}
-
-// dW[co][ci][i][j] = (A'^T S A')[i][j],  S_f[co][ci] at s[f*cout*cin + co*cin + ci]
-// st: s is stored [component][cin][cout] (the grouped reduction ran with its operands swapped: hnd_wino2_wgrad_output_t)
-__global__ void wino2_wgrad_out_kernel(const float* __restrict__ s_, float* __restrict__ dw, int cout, int cin, int st) {
-  const long long total = (long long)cout * cin;
-  const size_t fs = (size_t)total;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const float* s = s_ + (st ? (e % cin) * cout + e / cin : e) - e;
-    float t[2][5];
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-      const float m0 = s[(0 * 5 + j) * fs + e], m1 = s[(1 * 5 + j) * fs + e], m2 = s[(2 * 5 + j) * fs + e],
-                  m3 = s[(3 * 5 + j) * fs + e], m4 = s[(4 * 5 + j) * fs + e];
-      t[0][j] = m0 + m1 + m2 + m3;
-      t[1][j] = m1 - m2 + 2.f * m3 + m4;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      dw[e * 4 + i * 2 + 0] = t[i][0] + t[i][1] + t[i][2] + t[i][3];
-      dw[e * 4 + i * 2 + 1] = t[i][1] - t[i][2] + 2.f * t[i][3] + t[i][4];
-    }
-  }
-}
-
-
-// ================================================================================== F(6x6, 2x2) / F(2x2, 6x6)
-// Round 3: the same head convolutions on 6x6 output tiles.  Points {0, 1, -1, 2, -2, 1/2, inf}: 49 products per 36
-// outputs instead of 25 per 16 (12.9 % fewer GEMM flops; transformed tensors 1.36x instead of 1.56x the activation).
-// fp32 error against exact correlation, post-ReLU data, K = 256: relative L2 4.1e-6 (F(4x4,2x2): 1.7e-6).  Matrices by
-// Cook-Toom in exact rationals (all row scalings 1 / prod_{l != j}(a_j - a_l) sit in G, so B^T depends on the points
-// only and the weight-gradient problem F(2x2, 6x6) -- the dy tile in the role of the filter -- shares the forward
-// pass's V = B^T d B); checked against direct correlation in fp64 to 1e-15.
-constexpr float W6_AT[6][7] = {{1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f},
-                               {0.f, 1.f, -1.f, 2.f, -2.f, 1.f / 2.f, 0.f},
-                               {0.f, 1.f, 1.f, 4.f, 4.f, 1.f / 4.f, 0.f},
-                               {0.f, 1.f, -1.f, 8.f, -8.f, 1.f / 8.f, 0.f},
-                               {0.f, 1.f, 1.f, 16.f, 16.f, 1.f / 16.f, 0.f},
-                               {0.f, 1.f, -1.f, 32.f, -32.f, 1.f / 32.f, 1.f}};
-constexpr float W6_G[7][2] = {{-1.f / 2.f, 0.f},        {-1.f / 3.f, -1.f / 3.f}, {1.f / 9.f, -1.f / 9.f},
-                              {1.f / 36.f, 1.f / 18.f}, {-1.f / 60.f, 1.f / 30.f}, {32.f / 45.f, 16.f / 45.f},
-                              {0.f, 1.f}};
-constexpr float W6_BT[7][7] = {{-2.f, 4.f, 5.f / 2.f, -5.f, -1.f / 2.f, 1.f, 0.f},
-                               {0.f, 2.f, -2.f, -9.f / 2.f, 1.f / 2.f, 1.f, 0.f},
-                               {0.f, -2.f, 6.f, -7.f / 2.f, -3.f / 2.f, 1.f, 0.f},
-                               {0.f, 1.f, -3.f / 2.f, -2.f, 3.f / 2.f, 1.f, 0.f},
-                               {0.f, -1.f, 5.f / 2.f, 0.f, -5.f / 2.f, 1.f, 0.f},
-                               {0.f, 4.f, 0.f, -5.f, 0.f, 1.f, 0.f},
-                               {0.f, -2.f, 4.f, 5.f / 2.f, -5.f, -1.f / 2.f, 1.f}};
-constexpr float W6_G2[7][6] = {{-1.f / 2.f, 0.f, 0.f, 0.f, 0.f, 0.f},
-                               {-1.f / 3.f, -1.f / 3.f, -1.f / 3.f, -1.f / 3.f, -1.f / 3.f, -1.f / 3.f},
-                               {1.f / 9.f, -1.f / 9.f, 1.f / 9.f, -1.f / 9.f, 1.f / 9.f, -1.f / 9.f},
-                               {1.f / 36.f, 1.f / 18.f, 1.f / 9.f, 2.f / 9.f, 4.f / 9.f, 8.f / 9.f},
-                               {-1.f / 60.f, 1.f / 30.f, -1.f / 15.f, 2.f / 15.f, -4.f / 15.f, 8.f / 15.f},
-                               {32.f / 45.f, 16.f / 45.f, 8.f / 45.f, 4.f / 45.f, 2.f / 45.f, 1.f / 45.f},
-                               {0.f, 0.f, 0.f, 0.f, 0.f, 1.f}};
-constexpr float W6_A2T[2][7] = {{1.f, 1.f, 1.f, 1.f, 1.f, 1.f, 0.f}, {0.f, 1.f, -1.f, 2.f, -2.f, 1.f / 2.f, 1.f}};
-
-// out = M in for a compile-time matrix: fully unrolled, zero entries vanish, +-1 become add / subtract
-template <int R, int C, class V>
-__device__ __forceinline__ void mat_apply(const float (&M)[R][C], const V (&in)[C], V (&out)[R]) {
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    V acc = in[0] * 0.f;
-    bool first = true;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-      const float m = M[r][c];
-      if (m == 0.f) continue;
-      const V term = m == 1.f ? in[c] : (m == -1.f ? -in[c] : in[c] * m);
-      acc = first ? term : acc + term;
-      first = false;
-    }
-    out[r] = acc;
-  }
-}
-
-__global__ void wino26_weights_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin, int dgrad,
-                                      int rows, int rows_pad, int kdim) {
-  const long long total = (long long)rows_pad * kdim;
-  const int kreal = dgrad ? cout : cin;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int pr = (int)(e / kdim), k = (int)(e - (long long)pr * kdim);      // packed row pr holds channel r
-    const int r = hnd::chan_of_row(pr);
-    const bool ok = r < rows && k < kreal;
-    float g[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float v = 0.f;
-        if (ok) v = dgrad ? w[(((size_t)k * cin + r) * 2 + (1 - i)) * 2 + (1 - j)]
-                          : w[(((size_t)r * cin + k) * 2 + i) * 2 + j];
-        g[i][j] = v;
-      }
-    float t[2][7];                          // t[j] = G g[:, j]
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const float col[2] = {g[0][j], g[1][j]};
-      mat_apply(W6_G, col, t[j]);
-    }
-    const size_t fs = (size_t)rows_pad * kdim;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const float row[2] = {t[0][i], t[1][i]};
-      float o[7];
-      mat_apply(W6_G, row, o);
-      float* dst = u + ((size_t)(i * 7) * rows_pad + pr) * kdim + k;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) dst[(size_t)j * fs] = o[j];
-    }
-  }
-}
-
-__global__ void __launch_bounds__(256) wino26_input_kernel(const float* __restrict__ x, float* __restrict__ v,
-                                                           const Wino2Geom g, const float* __restrict__ pro_scale,
-                                                           const float* __restrict__ pro_shift, int pro_relu) {
-  const int c2n = g.c >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
-  const size_t fs = (size_t)g.tiles_pad * g.c;
-  for (long long e = hnd::xcd_contiguous_block() * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 ps = {1.f, 1.f}, pb = {0.f, 0.f};
-    if (pro_scale) {
-      ps = *(const f32x2*)(pro_scale + c2 * 2);
-      pb = *(const f32x2*)(pro_shift + c2 * 2);
-    }
-    const float floor_ = pro_relu ? 0.f : -INFINITY;
-    f32x2 d[7][7];                          // d[j][i]: column j of the patch (so a column is one array)
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int iy = 6 * ty - g.pad + i;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const int ix = 6 * tx - g.pad + j;
-        const bool ok = (unsigned)iy < (unsigned)g.h && (unsigned)ix < (unsigned)g.w;
-        const size_t off = ok ? (((size_t)b * g.h + iy) * g.w + ix) * g.c + c2 * 2 : 0;
-        f32x2 a = *(const f32x2*)(x + off);
-        if (pro_scale) {
-          a = a * ps + pb;
-          a.x = fmaxf(a.x, floor_); a.y = fmaxf(a.y, floor_);
-        }
-        const f32x2 z = {0.f, 0.f};
-        d[j][i] = ok ? a : z;
-      }
-    }
-    f32x2 r[7][7];                          // r[i][j] = (B^T d)[i][j]
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      f32x2 o[7];
-      mat_apply(W6_BT, d[j], o);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) r[i][j] = o[i];
-    }
-    float* dst = v + (size_t)t * g.c + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      f32x2 o[7];
-      mat_apply(W6_BT, r[i], o);
-#pragma unroll
-      for (int j = 0; j < 7; ++j) *(f32x2*)(dst + (size_t)(i * 7 + j) * fs) = o[j];
-    }
-  }
-}
-
+// ---------------------------------------------------------------------------------- 2x2 output
 // BatchNorm BACKWARD statistics of the tensor this launch produces (BWD): when the output is the gradient g w.r.t. the output
 // of a train-mode BatchNorm(+ReLU) -- the data gradient of the NEXT head conv -- the per-channel sums of
 // d = g [bn(x) > 0] and d * xhat that hnd_bn_bwd_reduce would make in a pass of its own (reading g and x: 8 B per element)
@@ -1073,59 +361,48 @@ struct BnBwdStatsArgs {
   int relu;
 };
 
-template <bool BWD>
-__global__ void __launch_bounds__(256) wino26_output_kernel(const float* __restrict__ m, float* __restrict__ y,
-                                                            const Wino2Geom g, int cout, int ldc,
-                                                            const float* __restrict__ epi_scale,
-                                                            const float* __restrict__ epi_shift, int relu,
-                                                            float* __restrict__ stats, const BnBwdStatsArgs bw) {
-  __shared__ float red[2][512];
+// Output transform (+ scale/shift, ReLU) of the 2x2 Winograd conv.  With `stats`, every block also writes the partial
+// (sum v, sum v^2) per output channel of the values it stored -> stats[blockIdx][2][cout]: the train-mode BatchNorm
+// statistics hnd_bn_finalize consumes (ntiles = gridDim.x); BWD: the BatchNorm-backward sums above instead.  Requires
+// 512 % cout == 0 so a thread keeps its channels.
+template <class S, bool BWD>
+__global__ void __launch_bounds__(S::kLaunchBound)
+wino2_output_kernel(const float* __restrict__ m, float* __restrict__ y, const Wino2Geom g, int cout, int ldc,
+                    const float* __restrict__ epi_scale, const float* __restrict__ epi_shift, int relu,
+                    float* __restrict__ stats, const BnBwdStatsArgs bw) {
+  constexpr int T = S::T;
   const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
+  const long long total = (long long)g.n * g.th * g.tw * c2n;
   const size_t fs = (size_t)g.tiles_pad * cout;
   f32x2 bsc = {1.f, 1.f}, bsh = {0.f, 0.f}, bmu = {0.f, 0.f}, brs = {1.f, 1.f};
   if (BWD) {        // (a thread's channel pair is the same in every iteration: 256 % (cout / 2) == 0)
-    const int c2b = (int)((blockIdx.x * (long long)blockDim.x + threadIdx.x) % c2n);
+    const int c2b = (int)(first_item<false>() % c2n);
     bsc = *(const f32x2*)(bw.scale + c2b * 2); bsh = *(const f32x2*)(bw.shift + c2b * 2);
     bmu = *(const f32x2*)(bw.mean + c2b * 2); brs = *(const f32x2*)(bw.rstd + c2b * 2);
   }
   f32x2 s1 = {0.f, 0.f}, s2 = {0.f, 0.f};
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    const float* src = m + (size_t)t * cout + c2 * 2;
-    f32x2 s[6][7];                          // s[a][j] = (A^T m)[a][j]
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      f32x2 col[7], o[6];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) col[i] = HND_NT_LOAD((const f32x2*)(src + (size_t)(i * 7 + j) * fs));
-      mat_apply(W6_AT, col, o);
-#pragma unroll
-      for (int a = 0; a < 6; ++a) s[a][j] = o[a];
-    }
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, c2n, g.th, g.tw);
+    const int c2 = it.c, tx = it.tx, ty = it.ty, b = it.b;
+    f32x2 s[T][S::P];
+    load_at<S>(m + (size_t)it.t * cout + c2 * 2, fs, s);
     f32x2 es = {1.f, 1.f}, eb = {0.f, 0.f};
     if (epi_scale) es = *(const f32x2*)(epi_scale + c2 * 2);
     if (epi_shift) eb = *(const f32x2*)(epi_shift + c2 * 2);
     arrive(es, eb);
-    auto emit = [&](auto checked) {         // see wino4_output_kernel: interior tiles store without branches
+    auto emit = [&](auto checked) {         // see wino3_output_kernel: interior tiles store without branches
       constexpr bool CHK = decltype(checked)::value;
 #pragma unroll
-      for (int a = 0; a < 6; ++a) {
-        const int oy = 6 * ty + a;
-        f32x2 o[6];
-        mat_apply(W6_AT, s[a], o);
+      for (int a = 0; a < T; ++a) {
+        const int oy = T * ty + a;
+        f32x2 o[T];
+        S::at(s[a], o);
 #pragma unroll
-        for (int bb = 0; bb < 6; ++bb) {
-          const int ox = 6 * tx + bb;
+        for (int bb = 0; bb < T; ++bb) {
+          const int ox = T * tx + bb;
           if (CHK && (oy >= g.oh || ox >= g.ow)) continue;
           f32x2 v = o[bb] * es + eb;
-          if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); }
+          if (relu) v = lanes_max(v, 0.f);
           const size_t yo = (((size_t)b * g.oh + oy) * g.ow + ox) * ldc + c2 * 2;
           *(f32x2*)(y + yo) = v;
           if (BWD) {
@@ -1145,70 +422,59 @@ __global__ void __launch_bounds__(256) wino26_output_kernel(const float* __restr
         }
       }
     };
-    if (6 * ty + 6 <= g.oh && 6 * tx + 6 <= g.ow) emit(std::false_type{});
+    if (T * ty + T <= g.oh && T * tx + T <= g.ow) emit(std::false_type{});
     else emit(std::true_type{});
   }
-  if (stats) {
-    red[0][threadIdx.x * 2] = s1.x; red[0][threadIdx.x * 2 + 1] = s1.y;
-    red[1][threadIdx.x * 2] = s2.x; red[1][threadIdx.x * 2 + 1] = s2.y;
-    __syncthreads();
-    if ((int)threadIdx.x < cout) {
-      float a1 = 0.f, a2 = 0.f;
-      for (int k = threadIdx.x; k < 512; k += cout) { a1 += red[0][k]; a2 += red[1][k]; }
-      float* st = stats + (size_t)blockIdx.x * 2 * cout;
-      st[threadIdx.x] = a1;
-      st[cout + threadIdx.x] = a2;
-    }
-  }
+  if (stats) block_stats_store(s1, s2, cout, stats);
 }
 
-// Z = G' dy_t G'^T of the 6x6 tiles of dy (F(2x2, 6x6): the weight gradient in the Winograd domain, see above)
-__global__ void __launch_bounds__(256) wino26_dy_kernel(const float* __restrict__ dy, float* __restrict__ z,
-                                                        const Wino2Geom g, int cout, int ldy) {
+// ---------------------------------------------------------------------------------- weight gradient: dy, output
+// Z = G' dy_t G'^T of the T x T tiles of dy (F(2x2, T x T): the weight gradient in the Winograd domain, winograd_schemes.h)
+template <class S>
+__global__ void __launch_bounds__(S::kLaunchBound)
+wino2_dy_kernel(const float* __restrict__ dy, float* __restrict__ z, const Wino2Geom g, int cout, int ldy) {
   const int c2n = cout >> 1;
-  const long long tiles = (long long)g.n * g.th * g.tw;
-  const long long total = tiles * c2n;
+  const long long total = (long long)g.n * g.th * g.tw * c2n;
   const size_t fs = (size_t)g.tiles_pad * cout;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % g.tw);
-    long long q = t / g.tw;
-    const int ty = (int)(q % g.th), b = (int)(q / g.th);
-    f32x2 d[6][6];                          // d[bb][a]: column bb of the dy tile
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, c2n, g.th, g.tw);
+    f32x2 d[S::T][S::T];
+    load_patch(d, dy, it.b, S::T * it.ty, S::T * it.tx, g.oh, g.ow, ldy, it.c * 2,
+               [&](size_t off) { return *(const f32x2*)(dy + off); });
+    transform_store<S::T, S::P>(d, z + (size_t)it.t * cout + it.c * 2, fs, [](const auto& in, auto& out) { S::gp(in, out); });
+  }
+}
+
+// dW[co][ci][i][j] = (A'^T S A')[i][j],  S_f[co][ci] at s[f*cout*cin + co*cin + ci], f = 0 .. P*P - 1
+// st: s is stored [component][cin][cout] (the grouped reduction ran with its operands swapped: hnd_wino2_wgrad_output_t)
+template <class S>
+__global__ void wino2_wgrad_out_kernel(const float* __restrict__ s_, float* __restrict__ dw, int cout, int cin, int st) {
+  constexpr int P = S::P;
+  const long long total = (long long)cout * cin;
+  const size_t fs = (size_t)total;
+  for (long long e = first_item<false>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const float* s = s_ + (st ? (e % cin) * cout + e / cin : e) - e;
+    float t[2][P];
 #pragma unroll
-    for (int a = 0; a < 6; ++a) {
-      const int oy = 6 * ty + a;
+    for (int j = 0; j < P; ++j) {
+      float col[P], o[2];
 #pragma unroll
-      for (int bb = 0; bb < 6; ++bb) {
-        const int ox = 6 * tx + bb;
-        const bool ok = oy < g.oh && ox < g.ow;
-        const size_t off = ok ? (((size_t)b * g.oh + oy) * g.ow + ox) * ldy + c2 * 2 : 0;
-        const f32x2 v = *(const f32x2*)(dy + off);
-        const f32x2 zz = {0.f, 0.f};
-        d[bb][a] = ok ? v : zz;
-      }
+      for (int i = 0; i < P; ++i) col[i] = s[(size_t)(i * P + j) * fs + e];
+      S::a2t(col, o);
+      t[0][j] = o[0];
+      t[1][j] = o[1];
     }
-    f32x2 r[7][6];                          // r[i][bb] = (G' dy)[i][bb]
 #pragma unroll
-    for (int bb = 0; bb < 6; ++bb) {
-      f32x2 o[7];
-      mat_apply(W6_G2, d[bb], o);
-#pragma unroll
-      for (int i = 0; i < 7; ++i) r[i][bb] = o[i];
-    }
-    float* dst = z + (size_t)t * cout + c2 * 2;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      f32x2 o[7];
-      mat_apply(W6_G2, r[i], o);
-#pragma unroll
-      for (int j = 0; j < 7; ++j) *(f32x2*)(dst + (size_t)(i * 7 + j) * fs) = o[j];
+    for (int i = 0; i < 2; ++i) {
+      float o[2];
+      S::a2t(t[i], o);
+      dw[e * 4 + i * 2 + 0] = o[0];
+      dw[e * 4 + i * 2 + 1] = o[1];
     }
   }
 }
 
+// ---------------------------------------------------------------------------------- fused BatchNorm-backward transforms
 // BatchNorm backward "apply" fused into BOTH consumers of its result (round 4).  For the two deep decoder convs (conv6,
 // conv7) the gradient w.r.t. the raw conv output, dy = k1 * d + k2 * x + k3 with d = [bn(x) > 0] * g, is read by exactly two
 // kernels: the input transform of the conv's data gradient (V = B^T dy B over 7x7 patches) and the dy transform of its
@@ -1228,106 +494,83 @@ __global__ void __launch_bounds__(256) wino26_bnbwd_transforms_kernel(
     const float* __restrict__ g, const float* __restrict__ x, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ k123, int relu, float* __restrict__ v,
     float* __restrict__ z, const BnBwdTransformGeom q) {
+  using S = F62;
+  constexpr int T = S::T, P = S::P;
   const int c2n = q.c >> 1;
   const long long total = (long long)q.n * q.th * q.tw * c2n;
   const size_t fs_d = (size_t)q.tiles_pad_d * q.c, fs_w = (size_t)q.tiles_pad_w * q.c;
-  for (long long e = hnd::xcd_contiguous_block() * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int c2 = (int)(e % c2n);
-    long long t = e / c2n;
-    const int tx = (int)(t % q.tw);
-    t /= q.tw;
-    const int ty = (int)(t % q.th), b = (int)(t / q.th);
+  for (long long e = first_item<true>(); e < total; e += (long long)gridDim.x * blockDim.x) {
+    const TileItem it = tile_item(e, c2n, q.th, q.tw);
+    const int c2 = it.c, tx = it.tx, ty = it.ty, b = it.b;
     const f32x2 sc = *(const f32x2*)(scale + c2 * 2), sh = *(const f32x2*)(shift + c2 * 2);
     const f32x2 k1 = *(const f32x2*)(k123 + c2 * 2), k2 = *(const f32x2*)(k123 + q.c + c2 * 2),
                 k3 = *(const f32x2*)(k123 + 2 * q.c + c2 * 2);
-    f32x2 d[7][7];                          // d[j][i]: column j of the dy patch
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      const int iy = 6 * ty - q.pad + i;
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        const int ix = 6 * tx - q.pad + j;
-        const bool ok = (unsigned)iy < (unsigned)q.oh && (unsigned)ix < (unsigned)q.ow;
-        const size_t off = ok ? (((size_t)b * q.oh + iy) * q.ow + ix) * q.c + c2 * 2 : 0;
-        f32x2 dd = *(const f32x2*)(g + off);
-        const f32x2 xv = *(const f32x2*)(x + off);
-        if (relu) {
-          const f32x2 out = xv * sc + sh;
-          dd.x = out.x > 0.f ? dd.x : 0.f;
-          dd.y = out.y > 0.f ? dd.y : 0.f;
-        }
-        const f32x2 val = k1 * dd + k2 * xv + k3;
-        const f32x2 zz = {0.f, 0.f};
-        d[j][i] = ok ? val : zz;
+    f32x2 d[P][P];                          // the dy patch
+    load_patch(d, g, b, T * ty - q.pad, T * tx - q.pad, q.oh, q.ow, q.c, c2 * 2, [&](size_t off) {
+      f32x2 dd = *(const f32x2*)(g + off);
+      const f32x2 xv = *(const f32x2*)(x + off);
+      if (relu) {
+        const f32x2 out = xv * sc + sh;
+        dd.x = out.x > 0.f ? dd.x : 0.f;
+        dd.y = out.y > 0.f ? dd.y : 0.f;
       }
-    }
+      return k1 * dd + k2 * xv + k3;
+    });
     if (ty < q.th_w && tx < q.tw_w) {       // Z = G' dy G'^T of the 6x6 tile: patch rows / columns pad .. pad + 5
-      f32x2 r[7][6];
+      f32x2 dt[T][T];
 #pragma unroll
-      for (int bb = 0; bb < 6; ++bb) {
-        f32x2 col[6], o[7];
+      for (int bb = 0; bb < T; ++bb)
 #pragma unroll
-        for (int a = 0; a < 6; ++a) col[a] = q.pad ? d[bb + 1][a + 1] : d[bb][a];
-        mat_apply(W6_G2, col, o);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) r[i][bb] = o[i];
-      }
-      float* dst = z + ((size_t)((size_t)b * q.th_w + ty) * q.tw_w + tx) * q.c + c2 * 2;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        f32x2 o[7];
-        mat_apply(W6_G2, r[i], o);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) *(f32x2*)(dst + (size_t)(i * 7 + j) * fs_w) = o[j];
-      }
+        for (int a = 0; a < T; ++a) dt[bb][a] = q.pad ? d[bb + 1][a + 1] : d[bb][a];
+      transform_store<T, P>(dt, z + ((size_t)((size_t)b * q.th_w + ty) * q.tw_w + tx) * q.c + c2 * 2, fs_w,
+                            [](const auto& in, auto& out) { S::gp(in, out); });
     }
-    if (ty < q.th_d && tx < q.tw_d) {       // V = B^T dy B of the 7x7 patch
-      f32x2 r[7][7];
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        f32x2 o[7];
-        mat_apply(W6_BT, d[j], o);
-#pragma unroll
-        for (int i = 0; i < 7; ++i) r[i][j] = o[i];
-      }
-      float* dst = v + ((size_t)((size_t)b * q.th_d + ty) * q.tw_d + tx) * q.c + c2 * 2;
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        f32x2 o[7];
-        mat_apply(W6_BT, r[i], o);
-#pragma unroll
-        for (int j = 0; j < 7; ++j) *(f32x2*)(dst + (size_t)(i * 7 + j) * fs_d) = o[j];
-      }
-    }
+    if (ty < q.th_d && tx < q.tw_d)         // V = B^T dy B of the 7x7 patch
+      transform_store<P, P>(d, v + ((size_t)((size_t)b * q.th_d + ty) * q.tw_d + tx) * q.c + c2 * 2, fs_d,
+                            [](const auto& in, auto& out) { S::bt(in, out); });
   }
 }
 
-// dW[co][ci][i][j] = (A'^T S A')[i][j],  S_f[co][ci] at s[f*cout*cin + co*cin + ci], f = 0..48
-__global__ void wino26_wgrad_out_kernel(const float* __restrict__ s_, float* __restrict__ dw, int cout, int cin, int st) {
-  const long long total = (long long)cout * cin;
-  const size_t fs = (size_t)total;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const float* s = s_ + (st ? (e % cin) * cout + e / cin : e) - e;
-    float t[2][7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      float col[7], o[2];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) col[i] = s[(size_t)(i * 7 + j) * fs + e];
-      mat_apply(W6_A2T, col, o);
-      t[0][j] = o[0];
-      t[1][j] = o[1];
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      float o[2];
-      mat_apply(W6_A2T, t[i], o);
-      dw[e * 4 + i * 2 + 0] = o[0];
-      dw[e * 4 + i * 2 + 1] = o[1];
-    }
+// ---------------------------------------------------------------------------------- host side
+inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
+
+// tiles of n maps of h x w outputs
+inline long long tiles_of(int n, int h, int w, int tile) { return (long long)n * ceil_div(h, tile) * ceil_div(w, tile); }
+inline int tiles_pad_of(int n, int h, int w, int tile) { return (int)((tiles_of(n, h, w, tile) + 127) / 128 * 128); }
+
+inline WinoGeom wino_geom(int n, int h, int w, int c, int tile) {
+  return WinoGeom{n, h, w, c, ceil_div(h, tile), ceil_div(w, tile), tiles_pad_of(n, h, w, tile)};
+}
+
+// h x w: the input (0 x 0 where the launch only sees the output side), oh x ow: the tiled extent
+inline Wino2Geom wino2_geom(int n, int h, int w, int c, int oh, int ow, int pad, int tile) {
+  return Wino2Geom{n, h, w, c, oh, ow, ceil_div(oh, tile), ceil_div(ow, tile), tiles_pad_of(n, oh, ow, tile), pad};
+}
+
+inline bool wino3_tile_ok(int tile) { return tile == 2 || tile == 4 || tile == 6; }
+inline bool wino2_tile_ok(int tile) { return tile == 4 || tile == 6; }
+
+// fn(scheme) for the scheme F(tile x tile, TAPS x TAPS); the tile has passed wino3_tile_ok / wino2_tile_ok
+template <int TAPS, class Fn>
+void with_scheme(int tile, Fn fn) {
+  if constexpr (TAPS == 3) {
+    if (tile == 2) fn(F23{});
+    else if (tile == 4) fn(F43{});
+    else fn(F63{});
+  } else {
+    if (tile == 4) fn(F42{});
+    else fn(F62{});
   }
+}
+
+template <int TAPS>
+void launch_weights(const float* weight, float* u, int cout, int cin, int dgrad, int tile, void* stream) {
+  const int rows = dgrad ? cin : cout, kreal = dgrad ? cout : cin;
+  const int rows_pad = (rows + 63) / 64 * 64;
+  with_scheme<TAPS>(tile, [&](auto s) {
+    hipLaunchKernelGGL(wino_weights_kernel<decltype(s)>, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
+                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
+  });
 }
 
 }  // namespace
@@ -1335,26 +578,16 @@ __global__ void wino26_wgrad_out_kernel(const float* __restrict__ s_, float* __r
 extern "C" {
 
 int64_t hnd_wino_tiles_pad(int n, int h, int w, int tile) {
-  if (tile != 2 && tile != 4 && tile != 6) return -1;
-  const long long t = (long long)n * ((h + tile - 1) / tile) * ((w + tile - 1) / tile);
-  return (t + 127) / 128 * 128;
+  if (!wino3_tile_ok(tile)) return -1;
+  return tiles_pad_of(n, h, w, tile);
 }
 
 int hnd_wino_weights(const float* weight, float* u, int cout, int cin, int dgrad, int tile, void* stream) {
   HND_REQUIRE(weight && u && cout > 0 && cin > 0 && (tile == 2 || tile == 4 || tile == 6),
               "hnd_wino_weights: bad arguments");
-  const int rows = dgrad ? cin : cout, kreal = dgrad ? cout : cin;
+  const int kreal = dgrad ? cout : cin;
   HND_REQUIRE(kreal % 32 == 0, "hnd_wino_weights: GEMM depth %d must be a multiple of 32", kreal);
-  const int rows_pad = (rows + 63) / 64 * 64;
-  if (tile == 2)
-    hipLaunchKernelGGL(wino_weights_kernel, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
-                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
-  else if (tile == 4)
-    hipLaunchKernelGGL(wino4_weights_kernel, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
-                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
-  else
-    hipLaunchKernelGGL(wino6_weights_kernel, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
-                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
+  launch_weights<3>(weight, u, cout, cin, dgrad, tile, stream);
   return hnd::check_launch("hnd_wino_weights");
 }
 
@@ -1363,17 +596,12 @@ int hnd_wino_input(const float* x, float* v, int n, int h, int w, int c, const f
   HND_REQUIRE(x && v && n > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && (tile == 2 || tile == 4 || tile == 6),
               "hnd_wino_input: bad arguments");
   HND_REQUIRE(pro_scale == nullptr || pro_shift != nullptr, "hnd_wino_input: pro_shift is required with pro_scale");
-  WinoGeom g{n, h, w, c, (h + tile - 1) / tile, (w + tile - 1) / tile, (int)hnd_wino_tiles_pad(n, h, w, tile)};
-  const long long tiles = (long long)n * g.th * g.tw;
-  if (tile == 2)
-    hipLaunchKernelGGL(wino_input_kernel, dim3(grid_for(tiles * (c / 4))), dim3(256), 0, hnd::as_stream(stream), x, v,
-                       g, pro_scale, pro_shift, pro_relu);
-  else if (tile == 4)
-    hipLaunchKernelGGL(wino4_input_kernel, dim3(grid_for(tiles * (c / 2))), dim3(256), 0, hnd::as_stream(stream), x, v,
-                       g, pro_scale, pro_shift, pro_relu);
-  else
-    hipLaunchKernelGGL(wino6_input_kernel, dim3(grid_for(tiles * (c / 2))), dim3(256), 0, hnd::as_stream(stream), x, v,
-                       g, pro_scale, pro_shift, pro_relu);
+  const WinoGeom g = wino_geom(n, h, w, c, tile);
+  with_scheme<3>(tile, [&](auto s) {
+    using S = decltype(s);
+    hipLaunchKernelGGL(wino_input_kernel<S>, dim3(grid_for(tiles_of(n, h, w, tile) * (c / lanes_of<typename S::V>))),
+                       dim3(256), 0, hnd::as_stream(stream), x, v, g, pro_scale, pro_shift, pro_relu);
+  });
   return hnd::check_launch("hnd_wino_input");
 }
 
@@ -1383,56 +611,45 @@ int hnd_wino_output(const float* m, float* y, int n, int h, int w, int cout, int
   HND_REQUIRE(m && y && n > 0 && h > 0 && w > 0 && cout > 0 && cout % 4 == 0 && ldc >= cout && ldc % 4 == 0 &&
                   (tile == 2 || tile == 4 || tile == 6), "hnd_wino_output: bad arguments");
   HND_REQUIRE(!mask_out || (tile != 2 && cout == ldc), "hnd_wino_output: mask_out needs tile 4 / 6 and cout == ldc");
-  WinoGeom g{n, h, w, ldc, (h + tile - 1) / tile, (w + tile - 1) / tile, (int)hnd_wino_tiles_pad(n, h, w, tile)};
-  WinoEpilogue ep{epi_scale, epi_shift, res1, mask, relu, mask_out};
-  const long long tiles = (long long)n * g.th * g.tw;
-  if (tile == 2)
-    hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(tiles * (cout / 4))), dim3(256), 0, hnd::as_stream(stream), m,
-                       y, g, cout, ep);
-  else {
-    const dim3 grid(grid_for(tiles * (cout / 2))), block(256);
-    hipStream_t st = hnd::as_stream(stream);
-#define HND_WINO_OUT(K)                                                                          \
-  do {                                                                                           \
-    if (res1 && mask) hipLaunchKernelGGL((K<true, true>), grid, block, 0, st, m, y, g, cout, ep);   \
-    else if (res1) hipLaunchKernelGGL((K<true, false>), grid, block, 0, st, m, y, g, cout, ep);     \
-    else if (mask) hipLaunchKernelGGL((K<false, true>), grid, block, 0, st, m, y, g, cout, ep);     \
-    else hipLaunchKernelGGL((K<false, false>), grid, block, 0, st, m, y, g, cout, ep);              \
-  } while (0)
-    if (tile == 4) HND_WINO_OUT(wino4_output_kernel);
-    else HND_WINO_OUT(wino6_output_kernel);
-#undef HND_WINO_OUT
-  }
+  const WinoGeom g = wino_geom(n, h, w, ldc, tile);
+  const WinoEpilogue ep{epi_scale, epi_shift, res1, mask, relu, mask_out};
+  const long long tiles = tiles_of(n, h, w, tile);
+  hipStream_t st = hnd::as_stream(stream);
+  with_scheme<3>(tile, [&](auto s) {
+    using S = decltype(s);
+    if constexpr (std::is_same_v<S, F23>) {
+      hipLaunchKernelGGL(wino_output_kernel, dim3(grid_for(tiles * (cout / 4))), dim3(256), 0, st, m, y, g, cout, ep);
+    } else {
+      auto launch = [&](auto res, auto msk) {
+        hipLaunchKernelGGL((wino3_output_kernel<S, decltype(res)::value, decltype(msk)::value>),
+                           dim3(grid_for(tiles * (cout / 2))), dim3(256), 0, st, m, y, g, cout, ep);
+      };
+      if (res1 && mask) launch(std::true_type{}, std::true_type{});
+      else if (res1) launch(std::true_type{}, std::false_type{});
+      else if (mask) launch(std::false_type{}, std::true_type{});
+      else launch(std::false_type{}, std::false_type{});
+    }
+  });
   return hnd::check_launch("hnd_wino_output");
 }
 
 /* ---- F(4x4, 2x2) / F(6x6, 2x2): the 2x2 convolutions of the student head; tile = 4 or 6 ---- */
-static inline bool wino2_tile_ok(int tile) { return tile == 4 || tile == 6; }
-
 int64_t hnd_wino2_tiles_pad(int n, int oh, int ow, int tile) {
   if (!wino2_tile_ok(tile)) return -1;
-  const long long t = (long long)n * ((oh + tile - 1) / tile) * ((ow + tile - 1) / tile);
-  return (t + 127) / 128 * 128;
+  return tiles_pad_of(n, oh, ow, tile);
 }
 
 int hnd_wino2_stats_blocks(int n, int oh, int ow, int cout, int tile) {
   if (!wino2_tile_ok(tile)) return -1;
-  const long long tiles = (long long)n * ((oh + tile - 1) / tile) * ((ow + tile - 1) / tile);
-  long long b = (tiles * (cout / 2) + 255) / 256;
+  long long b = (tiles_of(n, oh, ow, tile) * (cout / 2) + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
 }
 
 int hnd_wino2_weights(const float* weight, float* u, int cout, int cin, int dgrad, int tile, void* stream) {
   HND_REQUIRE(weight && u && cout > 0 && cin > 0 && wino2_tile_ok(tile), "hnd_wino2_weights: bad arguments");
-  const int rows = dgrad ? cin : cout, kreal = dgrad ? cout : cin;
+  const int kreal = dgrad ? cout : cin;
   HND_REQUIRE(kreal % 32 == 0, "hnd_wino2_weights: GEMM depth %d must be a multiple of 32", kreal);
-  const int rows_pad = (rows + 63) / 64 * 64;
-  if (tile == 4)
-    hipLaunchKernelGGL(wino2_weights_kernel, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
-                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
-  else
-    hipLaunchKernelGGL(wino26_weights_kernel, dim3(grid_for((long long)rows_pad * kreal)), dim3(256), 0,
-                       hnd::as_stream(stream), weight, u, cout, cin, dgrad, rows, rows_pad, kreal);
+  launch_weights<2>(weight, u, cout, cin, dgrad, tile, stream);
   return hnd::check_launch("hnd_wino2_weights");
 }
 
@@ -1442,15 +659,11 @@ int hnd_wino2_input(const float* x, float* v, int n, int h, int w, int c, int pa
                   h + 2 * pad - 1 > 0 && w + 2 * pad - 1 > 0 && wino2_tile_ok(tile), "hnd_wino2_input: bad arguments");
   HND_REQUIRE(pro_scale == nullptr || pro_shift != nullptr, "hnd_wino2_input: pro_shift is required with pro_scale");
   const int oh = h + 2 * pad - 1, ow = w + 2 * pad - 1;
-  Wino2Geom g{n, h, w, c, oh, ow, (oh + tile - 1) / tile, (ow + tile - 1) / tile,
-              (int)hnd_wino2_tiles_pad(n, oh, ow, tile), pad};
-  const long long tiles = (long long)n * g.th * g.tw;
-  if (tile == 4)
-    hipLaunchKernelGGL(wino2_input_kernel, dim3(grid_for(tiles * (c / 2))), dim3(256), 0, hnd::as_stream(stream), x, v,
-                       g, pro_scale, pro_shift, pro_relu);
-  else
-    hipLaunchKernelGGL(wino26_input_kernel, dim3(grid_for(tiles * (c / 2))), dim3(256), 0, hnd::as_stream(stream), x, v,
-                       g, pro_scale, pro_shift, pro_relu);
+  const Wino2Geom g = wino2_geom(n, h, w, c, oh, ow, pad, tile);
+  with_scheme<2>(tile, [&](auto s) {
+    hipLaunchKernelGGL(wino_input_kernel<decltype(s)>, dim3(grid_for(tiles_of(n, oh, ow, tile) * (c / 2))), dim3(256), 0,
+                       hnd::as_stream(stream), x, v, g, pro_scale, pro_shift, pro_relu);
+  });
   return hnd::check_launch("hnd_wino2_input");
 }
 
@@ -1459,15 +672,12 @@ int hnd_wino2_output(const float* m, float* y, int n, int oh, int ow, int cout, 
   HND_REQUIRE(m && y && n > 0 && oh > 0 && ow > 0 && cout > 0 && cout % 2 == 0 && ldc >= cout && ldc % 2 == 0 &&
                   wino2_tile_ok(tile), "hnd_wino2_output: bad arguments");
   HND_REQUIRE(stats == nullptr || 512 % cout == 0, "hnd_wino2_output: stats need 512 %% cout == 0 (cout=%d)", cout);
-  Wino2Geom g{n, 0, 0, 0, oh, ow, (oh + tile - 1) / tile, (ow + tile - 1) / tile,
-              (int)hnd_wino2_tiles_pad(n, oh, ow, tile), 0};
+  const Wino2Geom g = wino2_geom(n, 0, 0, 0, oh, ow, 0, tile);
   const int blocks = hnd_wino2_stats_blocks(n, oh, ow, cout, tile);
-  if (tile == 4)
-    hipLaunchKernelGGL(wino2_output_kernel, dim3(blocks), dim3(256), 0, hnd::as_stream(stream), m, y, g, cout, ldc,
-                       epi_scale, epi_shift, relu, stats);
-  else
-    hipLaunchKernelGGL(wino26_output_kernel<false>, dim3(blocks), dim3(256), 0, hnd::as_stream(stream), m, y, g, cout,
-                       ldc, epi_scale, epi_shift, relu, stats, BnBwdStatsArgs{});
+  with_scheme<2>(tile, [&](auto s) {
+    hipLaunchKernelGGL((wino2_output_kernel<decltype(s), false>), dim3(blocks), dim3(256), 0, hnd::as_stream(stream), m, y,
+                       g, cout, ldc, epi_scale, epi_shift, relu, stats, BnBwdStatsArgs{});
+  });
   return hnd::check_launch("hnd_wino2_output");
 }
 
@@ -1477,10 +687,10 @@ int hnd_wino26_output_bnbwd_stats(const float* m, float* y, int n, int oh, int o
   HND_REQUIRE(m && y && x && scale && shift && mean && rstd && partials && n > 0 && oh > 0 && ow > 0 && cout > 0 &&
                   cout % 2 == 0 && ldc >= cout && ldc % 2 == 0 && 512 % cout == 0,
               "hnd_wino26_output_bnbwd_stats: bad arguments (cout=%d must divide 512)", cout);
-  Wino2Geom g{n, 0, 0, 0, oh, ow, (oh + 5) / 6, (ow + 5) / 6, (int)hnd_wino2_tiles_pad(n, oh, ow, 6), 0};
+  const Wino2Geom g = wino2_geom(n, 0, 0, 0, oh, ow, 0, 6);
   const int blocks = hnd_wino2_stats_blocks(n, oh, ow, cout, 6);
-  hipLaunchKernelGGL(wino26_output_kernel<true>, dim3(blocks), dim3(256), 0, hnd::as_stream(stream), m, y, g, cout, ldc,
-                     (const float*)nullptr, (const float*)nullptr, 0, partials,
+  hipLaunchKernelGGL((wino2_output_kernel<F62, true>), dim3(blocks), dim3(256), 0, hnd::as_stream(stream), m, y, g, cout,
+                     ldc, (const float*)nullptr, (const float*)nullptr, 0, partials,
                      BnBwdStatsArgs{x, scale, shift, mean, rstd, relu_of_bn});
   return hnd::check_launch("hnd_wino26_output_bnbwd_stats");
 }
@@ -1491,15 +701,11 @@ int hnd_wino26_output_bnbwd_stats(const float* m, float* y, int n, int oh, int o
 int hnd_wino2_dy(const float* dy, float* z, int n, int oh, int ow, int cout, int ldy, int tile, void* stream) {
   HND_REQUIRE(dy && z && n > 0 && oh > 0 && ow > 0 && cout > 0 && cout % 2 == 0 && ldy >= cout && ldy % 2 == 0 &&
                   wino2_tile_ok(tile), "hnd_wino2_dy: bad arguments");
-  Wino2Geom g{n, 0, 0, 0, oh, ow, (oh + tile - 1) / tile, (ow + tile - 1) / tile,
-              (int)hnd_wino2_tiles_pad(n, oh, ow, tile), 0};
-  const long long tiles = (long long)n * g.th * g.tw;
-  if (tile == 4)
-    hipLaunchKernelGGL(wino2_dy_kernel, dim3(grid_for(tiles * (cout / 2))), dim3(256), 0, hnd::as_stream(stream), dy,
-                       z, g, cout, ldy);
-  else
-    hipLaunchKernelGGL(wino26_dy_kernel, dim3(grid_for(tiles * (cout / 2))), dim3(256), 0, hnd::as_stream(stream), dy,
-                       z, g, cout, ldy);
+  const Wino2Geom g = wino2_geom(n, 0, 0, 0, oh, ow, 0, tile);
+  with_scheme<2>(tile, [&](auto s) {
+    hipLaunchKernelGGL(wino2_dy_kernel<decltype(s)>, dim3(grid_for(tiles_of(n, oh, ow, tile) * (cout / 2))), dim3(256), 0,
+                       hnd::as_stream(stream), dy, z, g, cout, ldy);
+  });
   return hnd::check_launch("hnd_wino2_dy");
 }
 
@@ -1512,8 +718,8 @@ int hnd_wino26_bnbwd_transforms(const float* g, const float* x, const float* sca
   const int ih = oh + 2 * pad - 1, iw = ow + 2 * pad - 1;      // extent of the data gradient's output (the conv input)
   BnBwdTransformGeom q;
   q.n = n; q.oh = oh; q.ow = ow; q.c = c; q.pad = pad;
-  q.th_d = (ih + 5) / 6; q.tw_d = (iw + 5) / 6; q.tiles_pad_d = (int)hnd_wino2_tiles_pad(n, ih, iw, 6);
-  q.th_w = (oh + 5) / 6; q.tw_w = (ow + 5) / 6; q.tiles_pad_w = (int)hnd_wino2_tiles_pad(n, oh, ow, 6);
+  q.th_d = ceil_div(ih, 6); q.tw_d = ceil_div(iw, 6); q.tiles_pad_d = tiles_pad_of(n, ih, iw, 6);
+  q.th_w = ceil_div(oh, 6); q.tw_w = ceil_div(ow, 6); q.tiles_pad_w = tiles_pad_of(n, oh, ow, 6);
   q.th = q.th_d > q.th_w ? q.th_d : q.th_w;
   q.tw = q.tw_d > q.tw_w ? q.tw_d : q.tw_w;
   const long long tiles = (long long)n * q.th * q.tw;
@@ -1524,12 +730,10 @@ int hnd_wino26_bnbwd_transforms(const float* g, const float* x, const float* sca
 
 int hnd_wino2_wgrad_output_t(const float* s, float* dw, int cout, int cin, int tile, int s_transposed, void* stream) {
   HND_REQUIRE(s && dw && cout > 0 && cin > 0 && wino2_tile_ok(tile), "hnd_wino2_wgrad_output: bad arguments");
-  if (tile == 4)
-    hipLaunchKernelGGL(wino2_wgrad_out_kernel, dim3(grid_for((long long)cout * cin)), dim3(256), 0,
+  with_scheme<2>(tile, [&](auto sch) {
+    hipLaunchKernelGGL(wino2_wgrad_out_kernel<decltype(sch)>, dim3(grid_for((long long)cout * cin)), dim3(256), 0,
                        hnd::as_stream(stream), s, dw, cout, cin, s_transposed ? 1 : 0);
-  else
-    hipLaunchKernelGGL(wino26_wgrad_out_kernel, dim3(grid_for((long long)cout * cin)), dim3(256), 0,
-                       hnd::as_stream(stream), s, dw, cout, cin, s_transposed ? 1 : 0);
+  });
   return hnd::check_launch("hnd_wino2_wgrad_output");
 }
 

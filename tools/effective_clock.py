@@ -22,6 +22,7 @@ def family(name):
                      ('bstream_kernel', 'bstream'), ('wgrad_ring_kernel', 'wgrad_ring'), ('igemm_kernel', 'igemm (tiled)'),
                      ('wgrad_kernel', 'wgrad (LDS-staged)'), ('stem7_wgrad', 'stem7_wgrad'), ('stem7_kernel', 'stem7_lds'),
                      ('wino6_input', 'wino6_input'), ('wino6_output', 'wino6_output'), ('wino26_', 'wino26_*'),
+                     ('wino_input_kernel<wino::F63', 'wino6_input'), ('wino3_output_kernel<wino::F63', 'wino6_output'), ('wino::F62', 'wino26_*'),
                      ('mse_kernel', 'mse'), ('maxpool', 'maxpool'), ('bn_bwd', 'bn_bwd_*'), ('affine_relu', 'affine_relu')):
         if key in name:
             return lab

@@ -56,6 +56,9 @@ def short(name):
             return lab
     if 'stem7_kernel' in name:
         return 'stem7_lds'
+    m = re.search(r'(wino\d?_\w+?)_kernel<(?:wino::)?(F\d\d)', name)
+    if m:           # one Winograd kernel per role, instantiated per scheme (winograd_schemes.h)
+        return '%s[%s]' % m.groups()
     for key in ('wino6_input', 'wino6_output', 'wino6_weights', 'wino4_input', 'wino4_output', 'wino4_weights', 'wino2_input', 'wino2_output', 'wino2_weights',
                 'wino_input', 'wino_output', 'wino_weights'):
         if key + '_kernel' in name:
