@@ -47,6 +47,9 @@ class BottleneckBase4Ext(nn.Module):
         # 1 ... 8 = in TRAIN mode the bottleneck tensor is quantised and dequantised at that width between encoder and
         # decoder, straight-through in the backward (HeadEngine.forward); None = off, the reference's training
         self.train_fake_quant_bits = None
+        # ... with a scale and a zero point per channel (an extension; yaml train.fake_quantize.per_channel; include/
+        # hnd_qchannel.h).  Read with train_fake_quant_bits; not together with train_fake_quant_range
+        self.train_fake_quant_per_channel = False
         # ... on a FIXED range (an extension; yaml train.fake_quantize.range: {type: ema}; include/hnd_qrange.h): see the
         # property train_fake_quant_range.  None = the range of each batch
         self._fq_range = None
@@ -136,6 +139,12 @@ class BottleneckBase4Ext(nn.Module):
             return None
         from ...structure.transformer import check_fake_quant_bits
         check_fake_quant_bits('train_fake_quant_bits (train.fake_quantize.num_bits)', bits)
+        if not isinstance(self.train_fake_quant_per_channel, bool):
+            raise ValueError('train_fake_quant_per_channel (train.fake_quantize.per_channel)=%r must be a bool'
+                             % (self.train_fake_quant_per_channel,))
+        if self.train_fake_quant_per_channel and self._fq_range is not None:
+            raise ValueError('train_fake_quant_per_channel together with train_fake_quant_range (train.fake_quantize.range: '
+                             '{type: ema}) is not built: the fixed range has no per-channel form')
         if self.encoder._forward_hooks:
             raise NotImplementedError(
                 'fake quantisation (train.fake_quantize) together with a hook / loss term on backbone.body.layer1.encoder '
@@ -161,7 +170,9 @@ class BottleneckBase4Ext(nn.Module):
                           codec=self.bottleneck_transformer if use_codec else None,   # base.py:54-57
                           fake_quant_bits=fq_bits,
                           **({} if fq_bits is None or self._fq_range is None
-                             else {'fake_quant_range': self._fake_quant_range_arg()}))
+                             else {'fake_quant_range': self._fake_quant_range_arg()}),
+                          **({} if fq_bits is None or not self.train_fake_quant_per_channel
+                             else {'fake_quant_per_channel': True}))
         body = self.__dict__.get('_body')
         z = None
         if self.encoder._forward_hooks or self.decoder._forward_hooks:

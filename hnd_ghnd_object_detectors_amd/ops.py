@@ -1007,6 +1007,122 @@ def entropy_decode_dequantize(payload, offsets, lengths, qparams, x, c, bits):
     return x
 
 
+# include/hnd_qchannel.h: one (scale, zero point) per channel.  qparams is device float[c][4] = {min, max, scale, zero_point}
+QCHANNEL_MAX_C = _lib.QCHANNEL_MAX_C
+
+
+def qchannel_abi():
+    return int(_L.hnd_qchannel_abi())
+
+
+def qchannel_scratch_elems(cs):
+    """floats of the `scratch` buffer of the quantising per-channel calls for a pixel stride of cs floats; 0 for a bad cs"""
+    return int(_L.hnd_qchannel_scratch_elems(int(cs)))
+
+
+def _qchannel_geometry(who, x, c, bits, dtype=torch.float32):
+    """(npix, cs) of the NHWC buffer x with c real channels, after the argument checks every per-channel wrapper shares"""
+    _qrange_bits(who, bits)
+    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.dim() >= 1 and x.is_contiguous()):
+        raise ValueError('%s: needs a contiguous %s NHWC buffer' % (who, str(dtype).replace('torch.', '')))
+    cs = x.shape[-1]
+    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= min(cs, QCHANNEL_MAX_C) or cs % 4 or x.numel() == 0:
+        raise ValueError('%s: c=%r real channels in a pixel stride of %d floats (0 < c <= stride, c <= %d, stride %% 4 == 0)'
+                         % (who, c, cs, QCHANNEL_MAX_C))
+    return x.numel() // cs, cs
+
+
+def _qchannel_qparams(who, qparams, c):
+    if not (isinstance(qparams, torch.Tensor) and qparams.dtype == torch.float32 and qparams.numel() == 4 * c
+            and qparams.is_contiguous()):
+        raise ValueError('%s: qparams must be a contiguous fp32 tensor [%d, 4]' % (who, c))
+    return qparams
+
+
+def _qchannel_scratch(who, scratch, cs):
+    if not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float32 and scratch.is_contiguous()
+            and scratch.numel() >= qchannel_scratch_elems(cs)):
+        raise ValueError('%s: scratch must be a contiguous fp32 buffer of qchannel_scratch_elems(%d) = %d floats'
+                         % (who, cs, qchannel_scratch_elems(cs)))
+    return scratch
+
+
+def _qchannel_payload(who, payload, x, c, bits):
+    n, h, w, _ = x.shape
+    if not (isinstance(payload, torch.Tensor) and payload.dtype == torch.uint8 and payload.is_contiguous()
+            and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0):
+        raise ValueError('%s: payload must be a contiguous uint8 buffer of codec_packed_bytes(%d, %d) = %d bytes'
+                         % (who, n * c * h * w, bits, codec_packed_bytes(n * c * h * w, bits)))
+    return n, h, w
+
+
+def qchannel_quantize_bits(x, c, bits, q, qparams, scratch):
+    """quantize_bits with the range of every channel its own: one value per byte into q (uint8, x's shape), pad channels 0"""
+    who = 'qchannel_quantize_bits'
+    npix, cs = _qchannel_geometry(who, x, c, bits)
+    if not (isinstance(q, torch.Tensor) and q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
+        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
+    check(_L.hnd_qchannel_quantize_bits(ptr(x), npix, c, cs, bits, ptr(q), ptr(_qchannel_qparams(who, qparams, c)),
+                                        ptr(_qchannel_scratch(who, scratch, cs)), stream_ptr()),
+          'hnd_qchannel_quantize_bits')
+
+
+def qchannel_dequantize_u8(q, qparams, x, c):
+    """the inverse: scale[ch] * (q - zero_point[ch]) into the c real channels of x, 0 into its pad channels"""
+    who = 'qchannel_dequantize_u8'
+    npix, cs = _qchannel_geometry(who, x, c, 8)
+    if not (isinstance(q, torch.Tensor) and q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
+        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
+    check(_L.hnd_qchannel_dequantize_u8(ptr(q), ptr(_qchannel_qparams(who, qparams, c)), ptr(x), npix, c, cs, stream_ptr()),
+          'hnd_qchannel_dequantize_u8')
+    return x
+
+
+def qchannel_quantize_pack_bits(x, c, bits, payload, qparams, scratch):
+    """quantize_pack_bits with the range of every channel its own: the payload format is that of include/hnd_codec.h"""
+    who = 'qchannel_quantize_pack_bits'
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise ValueError('%s: needs the NHWC buffer [N, H, W, cs]' % who)
+    _, cs = _qchannel_geometry(who, x, c, bits)
+    n, h, w = _qchannel_payload(who, payload, x, c, bits)
+    check(_L.hnd_qchannel_quantize_pack_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload),
+                                             ptr(_qchannel_qparams(who, qparams, c)),
+                                             ptr(_qchannel_scratch(who, scratch, cs)), stream_ptr()),
+          'hnd_qchannel_quantize_pack_bits')
+
+
+def qchannel_unpack_dequantize_bits(payload, qparams, x, c, bits):
+    """the inverse: scale[ch] * (q - zero_point[ch]) into the c real channels of x [N, H, W, cs], 0 into its pad channels"""
+    who = 'qchannel_unpack_dequantize_bits'
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise ValueError('%s: needs the NHWC buffer [N, H, W, cs]' % who)
+    _, cs = _qchannel_geometry(who, x, c, bits)
+    n, h, w = _qchannel_payload(who, payload, x, c, bits)
+    check(_L.hnd_qchannel_unpack_dequantize_bits(ptr(payload), ptr(_qchannel_qparams(who, qparams, c)), ptr(x), n, h, w, c,
+                                                 cs, bits, stream_ptr()), 'hnd_qchannel_unpack_dequantize_bits')
+    return x
+
+
+def qchannel_fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None):
+    """fake_quantize_bits with the range of every channel its own -- the bits of
+    qchannel_dequantize_u8(qchannel_quantize_bits(x)) -- into `out` (default: in place), 0 into the pad channels; `stats`
+    [fake_quantize_tiles(npix), 2, cs] receives the per-tile (sum, sum of squares) of what was stored, for bn_finalize.
+    Returns the destination."""
+    who = 'qchannel_fake_quantize_bits'
+    npix, cs = _qchannel_geometry(who, x, c, bits)
+    out = x if out is None else out
+    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
+            and tuple(out.shape) == tuple(x.shape)):
+        raise ValueError('%s: out must be a contiguous fp32 buffer of x\'s shape' % who)
+    if stats is not None and not (isinstance(stats, torch.Tensor) and stats.dtype == torch.float32 and stats.is_contiguous()
+                                  and stats.numel() == fake_quantize_tiles(npix) * 2 * cs):
+        raise ValueError('%s: stats must be a contiguous fp32 buffer [%d, 2, %d]' % (who, fake_quantize_tiles(npix), cs))
+    check(_L.hnd_qchannel_fake_quantize_bits(ptr(x), ptr(out), npix, c, cs, bits, ptr(_qchannel_qparams(who, qparams, c)),
+                                             ptr(_qchannel_scratch(who, scratch, cs)), ptr(stats), stream_ptr()),
+          'hnd_qchannel_fake_quantize_bits')
+    return out
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

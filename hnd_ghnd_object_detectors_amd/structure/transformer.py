@@ -4,7 +4,8 @@ The reference applies them ONLY at evaluation time with ``-transform_bottleneck`
 mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantizer`` run as fused HIP kernels
 (global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
 payload, include/hnd_codec.h, or entropy-coded in chunks, include/hnd_entropy.h; dequantise) on the NHWC bottleneck buffer;
-the 16-bit variants are a half round trip.
+the 16-bit variants are a half round trip.  ``per_channel=True`` (an extension, include/hnd_qchannel.h) gives every channel
+of the bottleneck a scale and a zero point of its own, in the plain, the packed and the fake quantiser.
 ``FakeQuantizer`` (an extension) is the pair as one call (include/hnd_qat.h) -- the launch the TRAINING step runs on the
 bottleneck tensor when ``train.fake_quantize`` is set (engine.HeadEngine.forward).
 ``JpegCompressor`` / ``JpegDecompressor`` (:94-128: the uint8 bottleneck image through a JPEG file)
@@ -190,7 +191,10 @@ class JpegCompressor(object):
     """reference :94-114: a 3-channel bottleneck ([3, H, W] or [1, 3, H, W]) is quantised to uint8 (HIP kernel),
     written as a JPEG file and replaced by ``(file path, quantised tensor)``; anything else passes through"""
 
-    def __init__(self, jpeg_quality=95, tmp_dir_path='./tmp/'):
+    def __init__(self, jpeg_quality=95, tmp_dir_path='./tmp/', per_channel=False):
+        if _check_per_channel('JpegCompressor', per_channel):
+            raise ValueError('JpegCompressor(per_channel=True): the JPEG file carries one scale and zero point; per-channel '
+                             'scales are built for Quantizer / FakeQuantizer at 1 ... 8 bits only')
         self.jpeg_quality, self.tmp_dir_path = jpeg_quality, tmp_dir_path
         os.makedirs(tmp_dir_path, exist_ok=True)
         self._quantizer = Quantizer(8)
@@ -231,11 +235,15 @@ class JpegDecompressor(object):
 
 class QuantizedTensor(object):
     """myutils tensor_util.QuantizedTensor: .tensor (uint8, logical NCHW), .scale, .zero_point.  scale / zero_point
-    are 0-dim DEVICE tensors (views of the kernel's qparams) so no host sync is forced; int()/float() work."""
+    are 0-dim DEVICE tensors (views of the kernel's qparams) so no host sync is forced; int()/float() work.
+    ``per_channel`` (an extension, include/hnd_qchannel.h): qparams is [c, 4], scale / zero_point are its 1-D views
+    qparams[:, 2] / qparams[:, 3], and ``num_bits`` is the width it was quantised at."""
 
-    def __init__(self, tensor, scale, zero_point, qparams=None, origin=None, channels=None):
+    def __init__(self, tensor, scale, zero_point, qparams=None, origin=None, channels=None, per_channel=False,
+                 num_bits=None):
         self.tensor, self.scale, self.zero_point = tensor, scale, zero_point
         self.qparams, self.origin, self.channels = qparams, origin, channels
+        self.per_channel, self.num_bits = bool(per_channel), num_bits
 
 
 class PackedBottleneck(object):
@@ -243,15 +251,22 @@ class PackedBottleneck(object):
     device tensor of exactly ceil(numel * num_bits / 8) bytes holding the values of the logical NCHW tensor ``shape``
     back to back, ``num_bits`` each, least significant bit first (format: include/hnd_codec.h); ``scale`` /
     ``zero_point`` are 0-dim device views of ``qparams`` as in QuantizedTensor.  An extension: the reference ships the
-    one-value-per-byte tensor whatever the width."""
+    one-value-per-byte tensor whatever the width.  ``per_channel`` (include/hnd_qchannel.h): the same payload format beside a
+    ``qparams`` of shape [c, 4]; ``scale`` / ``zero_point`` are its 1-D views qparams[:, 2] / qparams[:, 3]."""
 
-    def __init__(self, payload, shape, num_bits, qparams, origin=None):
+    def __init__(self, payload, shape, num_bits, qparams, origin=None, per_channel=False):
         self.payload, self.shape, self.num_bits = payload, tuple(int(s) for s in shape), num_bits
-        self.qparams, self.scale, self.zero_point, self.origin = qparams, qparams[2], qparams[3], origin
+        self.qparams, self.origin, self.per_channel = qparams, origin, bool(per_channel)
+        self.scale, self.zero_point = (qparams[:, 2], qparams[:, 3]) if self.per_channel else (qparams[2], qparams[3])
 
     @property
     def nbytes(self):
         return self.payload.numel()
+
+    @property
+    def link_bytes(self):
+        """everything that crosses the link: the payload and one (scale, zero point) per tensor or per channel"""
+        return self.nbytes + 8 * (self.shape[1] if self.per_channel else 1)
 
 
 MAX_CODE_LEN = 12          # longest code of include/hnd_entropy.h
@@ -361,6 +376,26 @@ def _check_bits(who, num_bits, packed=False):
             ' and packs 1 ... 8 bits only (16 is a half round trip, nothing to pack)' if packed else ''))
 
 
+def _check_per_channel(who, per_channel):
+    """``per_channel`` of Quantizer / FakeQuantizer / JpegCompressor: a bool, anything else is refused by name"""
+    if not isinstance(per_channel, bool):
+        raise ValueError('%s: per_channel=%r must be a bool' % (who, per_channel))
+    return per_channel
+
+
+def _check_per_channel_combination(who, num_bits, static_range, entropy=False):
+    """per-channel scales (include/hnd_qchannel.h) exist for the per-batch range at 1 ... 8 bits, plain, packed and fake
+    quantised; every other combination is refused by name"""
+    if entropy:
+        raise ValueError('%s(per_channel=True, entropy=True): the entropy coder has no per-channel form' % who)
+    if static_range is not None:
+        raise ValueError('%s(per_channel=True, static_range=%r): a fixed range has no per-channel form (per-channel scales '
+                         'come from the min / max of the tensor in front of the call)' % (who, static_range))
+    if num_bits == 16:
+        raise ValueError('%s(num_bits=16, per_channel=True): per-channel scales need a width of 1 ... 8 bits (16 is a half '
+                         'round trip, no scale)' % who)
+
+
 class _StaticRange(object):
     """``static_range`` of Quantizer / FakeQuantizer (include/hnd_qrange.h): None (min / max of the tensor in front of the
     call, three launches), a pair ``[lo, hi]`` (a fixed range: hnd_qrange_qparams runs once per pair and device, and every
@@ -433,18 +468,32 @@ class _StaticRange(object):
         return self._static_qparams[device]
 
 
-class Quantizer(_StaticRange):
+class _PerChannelKeyword(type):
+    """``Quantizer(..., per_channel=...)``: the keyword is taken off the call here and handed to ``_init_per_channel`` once
+    ``__init__`` has run, so ``Quantizer.__init__`` keeps the parameter list it has had since the entropy coder (callers and
+    tools that read it by ``inspect.signature`` see no change)"""
+
+    def __call__(cls, *args, per_channel=False, **kwargs):
+        self = super().__call__(*args, **kwargs)
+        self._init_per_channel(per_channel)
+        return self
+
+
+class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
     """reference :131-140 at any width the reference's uint8 tensor can hold: 1 ... 8 bits (qmax = 2^num_bits - 1), or
     16 (half round trip).  ``packed=True`` returns the bit-packed link payload (PackedBottleneck) instead of the
     one-value-per-byte QuantizedTensor.  ``static_range``: see _StaticRange (an extension).  ``entropy=True`` (an extension,
     1 ... 8 bits, not with ``packed``) runs the same quantise path and then entropy-codes its bytes (EntropyBottleneck,
     include/hnd_entropy.h): a histogram launch, one 1 KB read-back (the table depends on the data), huffman_lengths on the
     host and the encoder's three launches.  ``code_lengths`` (with ``entropy``) fixes the table instead -- all 2^num_bits
-    lengths non-zero -- and the call then has neither the histogram nor the read-back."""
+    lengths non-zero -- and the call then has neither the histogram nor the read-back.  ``per_channel=True`` (an extension,
+    1 ... 8 bits, plain or ``packed``; not with ``entropy`` or ``static_range``): min / max, scale and zero point per channel
+    (include/hnd_qchannel.h); the result carries ``per_channel=True`` and a ``qparams`` of shape [c, 4]."""
 
     def __init__(self, num_bits=8, packed=False, static_range=None, entropy=False, code_lengths=None):
         _check_bits('Quantizer', num_bits, packed)
         self.num_bits, self.packed, self.entropy = num_bits, bool(packed), bool(entropy)
+        self.per_channel = False            # (the keyword: _PerChannelKeyword / _init_per_channel)
         if self.entropy and self.packed:
             raise ValueError('Quantizer(entropy=True, packed=True): the link payload is either entropy-coded or bit-packed')
         if self.entropy and num_bits == 16:
@@ -456,6 +505,11 @@ class Quantizer(_StaticRange):
             check_code_lengths('Quantizer(entropy=True)', code_lengths, num_bits, complete=True)
         self._bufs, self._entropy_bufs = {}, {}
         self._init_static_range(static_range)
+
+    def _init_per_channel(self, per_channel):
+        self.per_channel = _check_per_channel('Quantizer', per_channel)
+        if self.per_channel:
+            _check_per_channel_combination('Quantizer', self.num_bits, self.static_range, self.entropy)
 
     def _entropy_code(self, q, c, qparams, shape, origin):
         """q (uint8 NHWC, one value per byte) -> EntropyBottleneck: [histogram, one 1 KB read-back, huffman_lengths] unless
@@ -485,12 +539,21 @@ class Quantizer(_StaticRange):
             return z, target
         key = (tuple(buf.shape), c, buf.device)
         if key not in self._bufs:
-            n, h, w, _ = buf.shape
+            n, h, w, cs = buf.shape
             qshape = (ops.codec_packed_bytes(n * c * h * w, self.num_bits),) if self.packed else buf.shape
             self._bufs[key] = (torch.empty(qshape, dtype=torch.uint8, device=buf.device),
-                               torch.empty(4, dtype=torch.float32, device=buf.device),
-                               torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
+                               torch.empty((c, 4) if self.per_channel else (4,), dtype=torch.float32, device=buf.device),
+                               torch.empty(ops.qchannel_scratch_elems(cs) if self.per_channel else
+                                           ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         q, qparams, scratch = self._bufs[key]
+        if self.per_channel:                # a scale and a zero point per channel (include/hnd_qchannel.h)
+            if self.packed:
+                ops.qchannel_quantize_pack_bits(buf, c, self.num_bits, q, qparams, scratch)
+                return PackedBottleneck(q, z.shape, self.num_bits, qparams, origin=buf, per_channel=True), target
+            ops.qchannel_quantize_bits(buf, c, self.num_bits, q, qparams, scratch)
+            qt = q[..., :c].permute(0, 3, 1, 2)
+            return QuantizedTensor(attach(qt, q), qparams[:, 2], qparams[:, 3], qparams, origin=buf, channels=c,
+                                   per_channel=True, num_bits=self.num_bits), target
         fixed = self._static_qparams_on(buf.device)
         if fixed is not None:               # one launch on the fixed range (include/hnd_qrange.h)
             if self.packed:
@@ -517,7 +580,9 @@ class Quantizer(_StaticRange):
 class Dequantizer(object):
     """reference :143-153.  A QuantizedTensor of any width goes through the one dequantise kernel (the width lives in its
     scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``; an
-    EntropyBottleneck is decoded and dequantised in one launch and must have been coded at ``num_bits``."""
+    EntropyBottleneck is decoded and dequantised in one launch and must have been coded at ``num_bits``.  A per-channel
+    QuantizedTensor / PackedBottleneck (``per_channel=True``, include/hnd_qchannel.h) is recognised by that attribute and
+    must have been quantised at ``num_bits``."""
 
     def __init__(self, num_bits=8):
         _check_bits('Dequantizer', num_bits)
@@ -531,7 +596,10 @@ class Dequantizer(object):
             n, c, h, w = qz.shape
             out = qz.origin if qz.origin is not None else \
                 torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
-            ops.unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
+            if qz.per_channel:
+                ops.qchannel_unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
+            else:
+                ops.unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
             return attach(out[..., :c].permute(0, 3, 1, 2), out), target
         if isinstance(qz, EntropyBottleneck):
             if qz.num_bits != self.num_bits:
@@ -542,11 +610,17 @@ class Dequantizer(object):
                 torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
             ops.entropy_decode_dequantize(qz.payload, qz.offsets, qz.lengths, qz.qparams, out, c, qz.num_bits)
             return attach(out[..., :c].permute(0, 3, 1, 2), out), target
+        if isinstance(qz, QuantizedTensor) and qz.per_channel and qz.num_bits != self.num_bits:
+            raise ValueError('Dequantizer(num_bits=%d) was handed a per-channel tensor quantised at %d bits'
+                             % (self.num_bits, qz.num_bits))
         if self.num_bits == 16 or not isinstance(qz, QuantizedTensor):
             return qz, target
         q = qz.tensor._hnd
         out = qz.origin if qz.origin is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
-        ops.dequantize_u8(q, qz.qparams, out, qz.channels)
+        if qz.per_channel:
+            ops.qchannel_dequantize_u8(q, qz.qparams, out, qz.channels)
+        else:
+            ops.dequantize_u8(q, qz.qparams, out, qz.channels)
         z = out[..., :qz.channels].permute(0, 3, 1, 2)
         return attach(z, out), target
 
@@ -566,10 +640,15 @@ class FakeQuantizer(_StaticRange):
     """``[Quantizer(num_bits), Dequantizer(num_bits)]`` as ONE codec call (include/hnd_qat.h): z -> the dequantised tensor,
     bit for bit what the pair returns, written back into z's buffer.  1 ... 8 bits; an extension (the reference has no
     such class).  ``qparams`` holds {min, max, scale, zero_point} of the newest call, on the device.  ``static_range``: see
-    _StaticRange; the call is then hnd_fake_quantize_range alone."""
+    _StaticRange; the call is then hnd_fake_quantize_range alone.  ``per_channel=True`` (not with ``static_range``): the pair
+    ``[Quantizer(num_bits, per_channel=True), Dequantizer(num_bits)]`` as one call (include/hnd_qchannel.h); ``qparams`` is
+    then [c, 4]."""
 
-    def __init__(self, num_bits=8, static_range=None):
+    def __init__(self, num_bits=8, static_range=None, per_channel=False):
         self.num_bits = check_fake_quant_bits('FakeQuantizer', num_bits)
+        self.per_channel = _check_per_channel('FakeQuantizer', per_channel)
+        if self.per_channel:
+            _check_per_channel_combination('FakeQuantizer', num_bits, static_range)
         self._bufs = {}
         self.qparams = None
         self._init_static_range(static_range)
@@ -584,11 +663,22 @@ class FakeQuantizer(_StaticRange):
             if getattr(z, '_hnd', None) is buf:
                 return z, target
             return attach(buf[..., :z.shape[1]].permute(0, 3, 1, 2), buf), target
+        c = z.shape[1]
+        if self.per_channel:                # a scale and a zero point per channel (include/hnd_qchannel.h)
+            key = (buf.device, c, buf.shape[-1])
+            if key not in self._bufs:
+                self._bufs[key] = (torch.empty((c, 4), dtype=torch.float32, device=buf.device),
+                                   torch.empty(ops.qchannel_scratch_elems(buf.shape[-1]), dtype=torch.float32,
+                                               device=buf.device))
+            self.qparams, scratch = self._bufs[key]
+            ops.qchannel_fake_quantize_bits(buf, c, self.num_bits, self.qparams, scratch)
+            if getattr(z, '_hnd', None) is buf:
+                return z, target
+            return attach(buf[..., :c].permute(0, 3, 1, 2), buf), target
         if buf.device not in self._bufs:
             self._bufs[buf.device] = (torch.empty(4, dtype=torch.float32, device=buf.device),
                                       torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         self.qparams, scratch = self._bufs[buf.device]
-        c = z.shape[1]
         ops.fake_quantize_bits(buf, c, self.num_bits, self.qparams, scratch)
         if getattr(z, '_hnd', None) is buf:         # a HIP-path tensor: a view of the buffer just rewritten
             return z, target
