@@ -3,11 +3,7 @@
 // All are streaming passes: 16-byte accesses per lane, grid-stride over <= 2048*8 blocks,
 // per-wave shuffle reductions then per-block partials (no float atomics -> deterministic).
 #include "common.h"
-#include "hnd_codec.h"
-#include "hnd_qat.h"
-#include "hnd_qrange.h"
 
-#include <hip/hip_fp16.h>
 #include <float.h>
 #include <limits.h>
 #include <math.h>
@@ -1102,289 +1098,6 @@ __global__ void fill_kernel(float* x, long long n, float v) {
     x[e] = v;
 }
 
-// ------------------------------------------------------------------------------------ bottleneck codec
-constexpr int kMinMaxBlocks = 512;
-
-__global__ void minmax_kernel(const float* __restrict__ x, long long npix, int c, int cs, float* __restrict__ part) {
-  __shared__ float smin[4], smax[4];
-  float lo = INFINITY, hi = -INFINITY;
-  const long long total = npix * cs;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    if ((int)(e % cs) < c) {
-      const float v = x[e];
-      lo = fminf(lo, v);
-      hi = fmaxf(hi, v);
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  if ((threadIdx.x & 63) == 0) { smin[threadIdx.x >> 6] = lo; smax[threadIdx.x >> 6] = hi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[blockIdx.x * 2 + 0] = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
-    part[blockIdx.x * 2 + 1] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
-  }
-}
-
-// The codec is byte work: it must reproduce myutils.tensor_util.quantize_tensor bit for bit on identical fp32 input
-// (tests/test_ops_gpu.py, torch.equal on the bytes).  Every operation below is therefore a single correctly rounded
-// IEEE fp32 operation in the reference's order.  hipcc's __fdiv_rn / __fadd_rn / __fmul_rn are the plain operators,
-// so FMA contraction is switched off inside these three kernels (none of the expressions below has a multiply feeding
-// an add today; the pragma keeps it that way) and the division is the correctly rounded one (v_div_scale / fmas /
-// fixup sequence, checked in the ISA).
-__global__ void qparams_kernel(const float* __restrict__ part, int nblocks, float qmax, float* __restrict__ qp) {
-#pragma clang fp contract(off)
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = threadIdx.x; i < nblocks; i += 64) {
-    lo = fminf(lo, part[i * 2]);
-    hi = fmaxf(hi, part[i * 2 + 1]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  if (threadIdx.x == 0) {
-    const float scale = __fdiv_rn(__fsub_rn(hi, lo), qmax);        // (max - min) / (qmax - qmin), qmin = 0
-    float zp = __fsub_rn(0.f, __fdiv_rn(lo, scale));               // qmin - min / scale
-    zp = zp < 0.f ? 0.f : (zp > qmax ? qmax : zp);
-    qp[0] = lo; qp[1] = hi; qp[2] = scale; qp[3] = truncf(zp);     // int(zero_point)
-  }
-}
-
-__global__ void quantize_kernel(const float* __restrict__ x, long long npix, int c, int cs,
-                                const float* __restrict__ qp, float qmax, uint8_t* __restrict__ q) {
-#pragma clang fp contract(off)
-  const float scale = qp[2], zp = qp[3];
-  const long long total = npix * cs;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    float v = 0.f;
-    if ((int)(e % cs) < c) {
-      v = __fadd_rn(zp, __fdiv_rn(x[e], scale));                   // zero_point + x / scale
-      v = v < 0.f ? 0.f : (v > qmax ? qmax : v);                   // clamp_(qmin, qmax)
-      v = rintf(v);                                                // round_(): half to even
-    }
-    q[e] = (uint8_t)v;
-  }
-}
-
-__global__ void dequantize_kernel(const uint8_t* __restrict__ q, const float* __restrict__ qp, float* __restrict__ x,
-                                  long long npix, int c, int cs) {
-#pragma clang fp contract(off)
-  const float scale = qp[2], zp = qp[3];
-  const long long total = npix * cs;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x)
-    x[e] = ((int)(e % cs) < c) ? __fmul_rn(scale, __fsub_rn((float)q[e], zp)) : 0.f;      // scale * (q - zero_point)
-}
-
-// The bit-packed payload of include/hnd_codec.h: value i of the logical NCHW tensor sits in bits [i * bits, (i + 1) * bits)
-// of the byte stream, LSB first.  One thread owns a GROUP of 8 consecutive values = `bits` whole bytes starting at byte
-// group * bits, so no two threads share a byte and every store is a plain byte store.  The values of a group are gathered
-// from the NHWC buffer (a group may cross a row, a channel plane or an image) and quantised with quantize_kernel's fp32
-// sequence.  The last group holds numel % 8 values when that is not 0 and stores ceil(rem * bits / 8) bytes.
-__global__ void quantize_pack_kernel(const float* __restrict__ x, long long numel, int c, long long hw, int cs, int bits,
-                                     const float* __restrict__ qp, float qmax, uint8_t* __restrict__ payload) {
-#pragma clang fp contract(off)
-  const float scale = qp[2], zp = qp[3];
-  const long long groups = (numel + 7) >> 3;
-  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups;
-       g += (long long)gridDim.x * blockDim.x) {
-    const long long i0 = g << 3;
-    const int count = numel - i0 < 8 ? (int)(numel - i0) : 8;
-    long long plane = i0 / hw, pix = i0 - plane * hw;               // plane = img * c + ch
-    long long img = plane / c;
-    int ch = (int)(plane - img * c);
-    unsigned long long word = 0;
-    for (int k = 0; k < count; ++k) {
-      float v = __fadd_rn(zp, __fdiv_rn(x[(img * hw + pix) * cs + ch], scale));     // zero_point + x / scale
-      v = v < 0.f ? 0.f : (v > qmax ? qmax : v);                   // clamp_(qmin, qmax)
-      v = rintf(v);                                                // round_(): half to even
-      word |= (unsigned long long)(unsigned)v << (k * bits);
-      if (++pix == hw) {
-        pix = 0;
-        if (++ch == c) { ch = 0; ++img; }
-      }
-    }
-    const int nbytes = (count * bits + 7) >> 3;                    // `bits` for a full group
-    uint8_t* dst = payload + g * bits;
-    for (int b = 0; b < nbytes; ++b) dst[b] = (uint8_t)(word >> (8 * b));
-  }
-}
-
-// One thread per float of the NHWC destination: real channels read their value's bits (at most two bytes: bits <= 8; the
-// second byte is touched only when the value reaches into it, so never past the payload's last byte), pad channels get 0.
-__global__ void unpack_dequantize_kernel(const uint8_t* __restrict__ payload, const float* __restrict__ qp,
-                                         float* __restrict__ x, long long npix, int c, long long hw, int cs, int bits) {
-#pragma clang fp contract(off)
-  const float scale = qp[2], zp = qp[3];
-  const long long total = npix * cs;
-  const unsigned mask = (1u << bits) - 1u;
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < total;
-       e += (long long)gridDim.x * blockDim.x) {
-    const long long p = e / cs;
-    const int ch = (int)(e - p * cs);
-    float v = 0.f;
-    if (ch < c) {
-      const long long img = p / hw, pix = p - img * hw;
-      const long long bit = ((img * c + ch) * hw + pix) * bits;
-      const long long byte = bit >> 3;
-      const int sh = (int)(bit & 7);
-      unsigned two = payload[byte];
-      if (sh + bits > 8) two |= (unsigned)payload[byte + 1] << 8;
-      v = __fmul_rn(scale, __fsub_rn((float)((two >> sh) & mask), zp));             // scale * (q - zero_point)
-    }
-    x[e] = v;
-  }
-}
-
-// include/hnd_qat.h: quantise and dequantise in one pass (quantize_kernel's then dequantize_kernel's fp32 sequence, the code
-// kept in a register instead of a byte: (float)(uint8_t)q == q for the integers 0 ... 255), in place or not, with the
-// BatchNorm partial sums of what was stored.  One WAVE per tile of kFqRows pixels; the wave's lanes are laid out as
-// (row, channel group of 4) with the group fastest, so a wave's 16-byte loads cover consecutive bytes and a lane keeps its
-// group for the whole tile (64 / groups rows per pass; a pixel wider than 64 groups is walked 64 groups at a time).  The
-// per-lane sums meet in LDS and are added in row-slot order: a fixed order, no atomics.  x and y may be the same buffer
-// (every float is read and written by one lane), so neither is __restrict__.
-// include/hnd_qrange.h builds the same kernel with kMask: qparams are then a caller's fixed range, values may lie outside it,
-// and `mask` (when not null) receives per pixel and group one byte whose bit k says that channel 4 g + k was NOT clipped
-// (rint(u) inside [0, qmax]; false for a NaN) -- one plain byte store per lane beside its 16-byte store of y, a wave's bytes
-// consecutive like its loads.  Pad channels and the high nibble are 0.
-constexpr int kFqRows = HND_FAKE_QUANT_TILE_ROWS;
-constexpr int kFqWaves = 4;
-
-template <bool kMask>
-__global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const float* x, float* y, long long npix, int c,
-                                                                      int cs, const float* __restrict__ qp, float qmax,
-                                                                      float* __restrict__ stats, int ntiles,
-                                                                      uint8_t* __restrict__ mask) {
-#pragma clang fp contract(off)
-  __shared__ float red[kFqWaves][64][8];
-  const float scale = qp[2], zp = qp[3];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int groups = cs >> 2;
-  for (int t0 = blockIdx.x * kFqWaves; t0 < ntiles; t0 += gridDim.x * kFqWaves) {      // (uniform over the block)
-    const int tile = t0 + wave;
-    const long long row0 = (long long)tile * kFqRows;
-    const int rows = tile < ntiles ? (npix - row0 < kFqRows ? (int)(npix - row0) : kFqRows) : 0;
-    for (int gb = 0; gb < groups; gb += 64) {
-      const int gc = groups - gb < 64 ? groups - gb : 64;         // groups in this pass
-      const int slots = 64 / gc;                                  // rows per pass
-      const int gl = lane % gc, slot = lane / gc;
-      const int ch0 = (gb + gl) * 4;
-      float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
-      if (slot < slots) {
-        for (int r = slot; r < rows; r += slots) {
-          const long long e = (row0 + r) * cs + ch0;
-          const f32x4 v = *(const f32x4*)(x + e);
-          f32x4 o;
-          unsigned pass = 0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            float q = 0.f;
-            if (ch0 + k < c) {
-              q = __fadd_rn(zp, __fdiv_rn(v[k], scale));            // zero_point + x / scale
-              if (kMask) {
-                const float r = rintf(q);
-                pass |= (r >= 0.f && r <= qmax) ? 1u << k : 0u;    // not clipped (-0 passes, a NaN does not)
-              }
-              q = q < 0.f ? 0.f : (q > qmax ? qmax : q);           // clamp_(qmin, qmax)
-              q = rintf(q);                                        // round_(): half to even
-              q = __fmul_rn(scale, __fsub_rn(q, zp));              // scale * (q - zero_point)
-            }
-            o[k] = q;
-            s[k] += q;
-            ss[k] += q * q;
-          }
-          *(f32x4*)(y + e) = o;
-          if (kMask && mask != nullptr) mask[(row0 + r) * groups + gb + gl] = (uint8_t)pass;
-        }
-      }
-      if (stats != nullptr) {                                    // (uniform over the block)
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { red[wave][lane][k] = s[k]; red[wave][lane][4 + k] = ss[k]; }
-        __syncthreads();
-        if (rows > 0) {
-          for (int i = lane; i < gc * 8; i += 64) {
-            const int g = i >> 3, k = i & 7;
-            float acc = 0.f;
-            for (int sl = 0; sl < slots; ++sl) acc += red[wave][sl * gc + g][k];
-            stats[((size_t)tile * 2 + (k >> 2)) * cs + (gb + g) * 4 + (k & 3)] = acc;
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-}
-
-// include/hnd_qrange.h: qparams of a range (lo, hi) -- qparams_kernel's formula, operation by operation
-__device__ __forceinline__ void qrange_write_qparams(float lo, float hi, float qmax, float* __restrict__ qp) {
-#pragma clang fp contract(off)
-  const float scale = __fdiv_rn(__fsub_rn(hi, lo), qmax);          // (max - min) / (qmax - qmin), qmin = 0
-  float zp = __fsub_rn(0.f, __fdiv_rn(lo, scale));                 // qmin - min / scale
-  zp = zp < 0.f ? 0.f : (zp > qmax ? qmax : zp);
-  qp[0] = lo; qp[1] = hi; qp[2] = scale; qp[3] = truncf(zp);       // int(zero_point)
-}
-
-// one wave: the batch (lo, hi) from minmax_kernel's partials, folded into state = {running_min, running_max, steps, 0}
-__global__ void qrange_observe_kernel(const float* __restrict__ part, int nblocks, float momentum, float qmax,
-                                      float* __restrict__ state, float* __restrict__ qp) {
-#pragma clang fp contract(off)
-  float lo = INFINITY, hi = -INFINITY;
-  for (int i = threadIdx.x; i < nblocks; i += 64) {
-    lo = fminf(lo, part[i * 2]);
-    hi = fmaxf(hi, part[i * 2 + 1]);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fminf(lo, __shfl_xor(lo, o));
-    hi = fmaxf(hi, __shfl_xor(hi, o));
-  }
-  if (threadIdx.x == 0) {
-    float rmin = state[0], rmax = state[1];
-    const float steps = state[2];
-    if (steps == 0.f) {
-      rmin = lo;
-      rmax = hi;
-    } else {
-      rmin = __fadd_rn(rmin, __fmul_rn(momentum, __fsub_rn(lo, rmin)));
-      rmax = __fadd_rn(rmax, __fmul_rn(momentum, __fsub_rn(hi, rmax)));
-    }
-    state[0] = rmin; state[1] = rmax; state[2] = __fadd_rn(steps, 1.f); state[3] = 0.f;
-    qrange_write_qparams(rmin, rmax, qmax, qp);
-  }
-}
-
-__global__ void qrange_qparams_kernel(float lo, float hi, float qmax, float* __restrict__ qp) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) qrange_write_qparams(lo, hi, qmax, qp);
-}
-
-// the backward of the clipping: one thread per 4-channel group (one mask byte, one 16-byte load and store); a clipped real
-// channel gets +0, everything else -- pad channels included -- keeps its bits
-__global__ void qrange_mask_grad_kernel(float* __restrict__ g, const uint8_t* __restrict__ mask, long long ngroups, int c,
-                                        int groups) {
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < ngroups;
-       e += (long long)gridDim.x * blockDim.x) {
-    const int ch0 = (int)(e % groups) * 4;
-    const unsigned m = mask[e];
-    f32x4 v = *(const f32x4*)(g + e * 4);
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      if (ch0 + k < c && !((m >> k) & 1u)) v[k] = 0.f;
-    *(f32x4*)(g + e * 4) = v;
-  }
-}
-
-__global__ void roundtrip_f16_kernel(float* x, long long n) {
-  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < n; e += (long long)gridDim.x * blockDim.x)
-    x[e] = __half2float(__float2half(x[e]));
-}
-
 }  // namespace
 
 // ======================================================================================== C ABI
@@ -1839,206 +1552,6 @@ int hnd_add_inplace(float* x, const float* y, int64_t numel, void* stream) {
   hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(numel / 4)), dim3(256), 0, hnd::as_stream(stream), x, y,
                      (long long)(numel / 4));
   return hnd::check_launch("hnd_add_inplace");
-}
-
-size_t hnd_minmax_scratch_elems(void) { return 2 * kMinMaxBlocks; }
-
-int hnd_quantize_u8(const float* x, int64_t npix, int c, int cs, uint8_t* q, float* qparams, float* scratch,
-                    void* stream) {
-  HND_REQUIRE(x && q && qparams && scratch && npix > 0 && c > 0 && cs >= c, "hnd_quantize_u8: bad arguments");
-  hipStream_t s = hnd::as_stream(stream);
-  int nb = grid_for((long long)npix * cs);
-  if (nb > kMinMaxBlocks) nb = kMinMaxBlocks;
-  hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(256), 0, s, x, (long long)npix, c, cs, scratch);
-  hipLaunchKernelGGL(qparams_kernel, dim3(1), dim3(64), 0, s, scratch, nb, 255.f, qparams);
-  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, s, x, (long long)npix, c, cs,
-                     qparams, 255.f, q);
-  return hnd::check_launch("hnd_quantize_u8");
-}
-
-int hnd_dequantize_u8(const uint8_t* q, const float* qparams, float* x, int64_t npix, int c, int cs, void* stream) {
-  HND_REQUIRE(q && qparams && x && npix > 0 && c > 0 && cs >= c, "hnd_dequantize_u8: bad arguments");
-  hipLaunchKernelGGL(dequantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, hnd::as_stream(stream), q,
-                     qparams, x, (long long)npix, c, cs);
-  return hnd::check_launch("hnd_dequantize_u8");
-}
-
-// ---- include/hnd_codec.h: the codec at 1 ... 8 bits and the bit-packed payload
-int hnd_codec_abi(void) { return HND_CODEC_ABI; }
-
-size_t hnd_codec_packed_bytes(int64_t numel, int bits) {
-  if (numel <= 0 || bits < 1 || bits > 8) return 0;
-  return (size_t)(numel >> 3) * bits + (size_t)(((numel & 7) * bits + 7) >> 3);      // ceil(numel * bits / 8), no overflow
-}
-
-// the two launches every quantising export starts with: per-block min / max of the real channels, then qparams
-static void launch_qparams(const float* x, long long npix, int c, int cs, float qmax, float* qparams, float* scratch,
-                           hipStream_t s) {
-  int nb = grid_for(npix * cs);
-  if (nb > kMinMaxBlocks) nb = kMinMaxBlocks;
-  hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(256), 0, s, x, npix, c, cs, scratch);
-  hipLaunchKernelGGL(qparams_kernel, dim3(1), dim3(64), 0, s, scratch, nb, qmax, qparams);
-}
-
-int hnd_quantize_bits(const float* x, int64_t npix, int c, int cs, int bits, uint8_t* q, float* qparams, float* scratch,
-                      void* stream) {
-  HND_REQUIRE(x && q && qparams && scratch, "hnd_quantize_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c, "hnd_quantize_bits: bad geometry (npix > 0, c > 0, cs >= c)");
-  hipStream_t s = hnd::as_stream(stream);
-  const float qmax = (float)((1 << bits) - 1);
-  launch_qparams(x, (long long)npix, c, cs, qmax, qparams, scratch, s);
-  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, s, x, (long long)npix, c, cs,
-                     qparams, qmax, q);
-  return hnd::check_launch("hnd_quantize_bits");
-}
-
-int hnd_quantize_pack_bits(const float* x, int n, int h, int w, int c, int cs, int bits, uint8_t* payload, float* qparams,
-                           float* scratch, void* stream) {
-  HND_REQUIRE(x && payload && qparams && scratch, "hnd_quantize_pack_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_pack_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c,
-              "hnd_quantize_pack_bits: bad geometry (n, h, w, c > 0, cs >= c)");
-  hipStream_t s = hnd::as_stream(stream);
-  const float qmax = (float)((1 << bits) - 1);
-  const long long hw = (long long)h * w, npix = hw * n, numel = npix * c;
-  launch_qparams(x, npix, c, cs, qmax, qparams, scratch, s);
-  hipLaunchKernelGGL(quantize_pack_kernel, dim3(grid_for((numel + 7) / 8)), dim3(256), 0, s, x, numel, c, hw, cs, bits,
-                     qparams, qmax, payload);
-  return hnd::check_launch("hnd_quantize_pack_bits");
-}
-
-int hnd_unpack_dequantize_bits(const uint8_t* payload, const float* qparams, float* x, int n, int h, int w, int c, int cs,
-                               int bits, void* stream) {
-  HND_REQUIRE(payload && qparams && x, "hnd_unpack_dequantize_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_unpack_dequantize_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c,
-              "hnd_unpack_dequantize_bits: bad geometry (n, h, w, c > 0, cs >= c)");
-  const long long hw = (long long)h * w, npix = hw * n;
-  hipLaunchKernelGGL(unpack_dequantize_kernel, dim3(grid_for(npix * cs)), dim3(256), 0, hnd::as_stream(stream), payload,
-                     qparams, x, npix, c, hw, cs, bits);
-  return hnd::check_launch("hnd_unpack_dequantize_bits");
-}
-
-// ---- include/hnd_qat.h: the fake-quantised bottleneck of the training step
-int hnd_qat_abi(void) { return HND_QAT_ABI; }
-
-int hnd_fake_quantize_tiles(int64_t npix) {
-  if (npix <= 0) return 0;
-  const int64_t t = (npix + kFqRows - 1) / kFqRows;
-  return t > INT_MAX ? 0 : (int)t;
-}
-
-int hnd_fake_quantize_bits(const float* x, float* y, int64_t npix, int c, int cs, int bits, float* qparams, float* scratch,
-                           float* stats, void* stream) {
-  HND_REQUIRE(x && y && qparams && scratch, "hnd_fake_quantize_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_fake_quantize_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_fake_quantize_bits: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
-  const int ntiles = hnd_fake_quantize_tiles(npix);
-  HND_REQUIRE(ntiles > 0, "hnd_fake_quantize_bits: npix too large (the tile count must fit an int)");
-  HND_REQUIRE(((uintptr_t)x | (uintptr_t)y) % 16 == 0, "hnd_fake_quantize_bits: x and y must be 16-byte aligned");
-  hipStream_t s = hnd::as_stream(stream);
-  const float qmax = (float)((1 << bits) - 1);
-  launch_qparams(x, (long long)npix, c, cs, qmax, qparams, scratch, s);
-  int nb = (ntiles + kFqWaves - 1) / kFqWaves;
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  hipLaunchKernelGGL(fake_quantize_kernel<false>, dim3(nb), dim3(64 * kFqWaves), 0, s, x, y, (long long)npix, c, cs,
-                     qparams, qmax, stats, ntiles, (uint8_t*)nullptr);
-  return hnd::check_launch("hnd_fake_quantize_bits");
-}
-
-// ---- include/hnd_qrange.h: the fixed (EMA-calibrated) range
-int hnd_qrange_abi(void) { return HND_QRANGE_ABI; }
-
-static inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0;
-}
-
-int hnd_qrange_observe(const float* x, int64_t npix, int c, int cs, float momentum, int bits, float* state, float* qparams,
-                       float* scratch, void* stream) {
-  HND_REQUIRE(x && state && qparams && scratch, "hnd_qrange_observe: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_qrange_observe: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_qrange_observe: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
-  HND_REQUIRE(momentum > 0.f && momentum <= 1.f, "hnd_qrange_observe: momentum outside (0, 1]");
-  HND_REQUIRE(aligned16(x, state, qparams), "hnd_qrange_observe: x, state and qparams must be 16-byte aligned");
-  hipStream_t s = hnd::as_stream(stream);
-  int nb = grid_for((long long)npix * cs);
-  if (nb > kMinMaxBlocks) nb = kMinMaxBlocks;
-  hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(256), 0, s, x, (long long)npix, c, cs, scratch);
-  hipLaunchKernelGGL(qrange_observe_kernel, dim3(1), dim3(64), 0, s, scratch, nb, momentum, (float)((1 << bits) - 1), state,
-                     qparams);
-  return hnd::check_launch("hnd_qrange_observe");
-}
-
-int hnd_qrange_qparams(float lo, float hi, int bits, float* qparams, void* stream) {
-  HND_REQUIRE(qparams, "hnd_qrange_qparams: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_qrange_qparams: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(std::isfinite(lo) && std::isfinite(hi) && lo < hi, "hnd_qrange_qparams: the range needs finite lo < hi");
-  HND_REQUIRE(aligned16(qparams), "hnd_qrange_qparams: qparams must be 16-byte aligned");
-  hipLaunchKernelGGL(qrange_qparams_kernel, dim3(1), dim3(1), 0, hnd::as_stream(stream), lo, hi, (float)((1 << bits) - 1),
-                     qparams);
-  return hnd::check_launch("hnd_qrange_qparams");
-}
-
-int hnd_fake_quantize_range(const float* x, float* y, int64_t npix, int c, int cs, int bits, const float* qparams,
-                            uint8_t* mask, float* stats, void* stream) {
-  HND_REQUIRE(x && y && qparams, "hnd_fake_quantize_range: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_fake_quantize_range: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_fake_quantize_range: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
-  const int ntiles = hnd_fake_quantize_tiles(npix);
-  HND_REQUIRE(ntiles > 0, "hnd_fake_quantize_range: npix too large (the tile count must fit an int)");
-  HND_REQUIRE(aligned16(x, y, qparams), "hnd_fake_quantize_range: x, y and qparams must be 16-byte aligned");
-  int nb = (ntiles + kFqWaves - 1) / kFqWaves;
-  if (nb > kMaxBlocks) nb = kMaxBlocks;
-  hipLaunchKernelGGL(fake_quantize_kernel<true>, dim3(nb), dim3(64 * kFqWaves), 0, hnd::as_stream(stream), x, y,
-                     (long long)npix, c, cs, qparams, (float)((1 << bits) - 1), stats, ntiles, mask);
-  return hnd::check_launch("hnd_fake_quantize_range");
-}
-
-int hnd_qrange_mask_grad(float* g, const uint8_t* mask, int64_t npix, int c, int cs, void* stream) {
-  HND_REQUIRE(g && mask, "hnd_qrange_mask_grad: null pointer");
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_qrange_mask_grad: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
-  HND_REQUIRE(aligned16(g), "hnd_qrange_mask_grad: g must be 16-byte aligned");
-  const long long ngroups = (long long)npix * (cs / 4);
-  hipLaunchKernelGGL(qrange_mask_grad_kernel, dim3(grid_for(ngroups)), dim3(256), 0, hnd::as_stream(stream), g, mask,
-                     ngroups, c, cs / 4);
-  return hnd::check_launch("hnd_qrange_mask_grad");
-}
-
-int hnd_quantize_range_bits(const float* x, int64_t npix, int c, int cs, int bits, uint8_t* q, const float* qparams,
-                            void* stream) {
-  HND_REQUIRE(x && q && qparams, "hnd_quantize_range_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_range_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(npix > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_quantize_range_bits: bad geometry (npix > 0, c > 0, cs >= c, cs %% 4 == 0)");
-  HND_REQUIRE(aligned16(x, qparams), "hnd_quantize_range_bits: x and qparams must be 16-byte aligned");
-  hipLaunchKernelGGL(quantize_kernel, dim3(grid_for((long long)npix * cs)), dim3(256), 0, hnd::as_stream(stream), x,
-                     (long long)npix, c, cs, qparams, (float)((1 << bits) - 1), q);
-  return hnd::check_launch("hnd_quantize_range_bits");
-}
-
-int hnd_quantize_pack_range_bits(const float* x, int n, int h, int w, int c, int cs, int bits, uint8_t* payload,
-                                 const float* qparams, void* stream) {
-  HND_REQUIRE(x && payload && qparams, "hnd_quantize_pack_range_bits: null pointer");
-  HND_REQUIRE(bits >= 1 && bits <= 8, "hnd_quantize_pack_range_bits: bits %d outside 1 ... 8", bits);
-  HND_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && cs >= c && cs % 4 == 0,
-              "hnd_quantize_pack_range_bits: bad geometry (n, h, w, c > 0, cs >= c, cs %% 4 == 0)");
-  HND_REQUIRE(aligned16(x, qparams), "hnd_quantize_pack_range_bits: x and qparams must be 16-byte aligned");
-  const long long hw = (long long)h * w, numel = hw * n * c;
-  hipLaunchKernelGGL(quantize_pack_kernel, dim3(grid_for((numel + 7) / 8)), dim3(256), 0, hnd::as_stream(stream), x, numel,
-                     c, hw, cs, bits, qparams, (float)((1 << bits) - 1), payload);
-  return hnd::check_launch("hnd_quantize_pack_range_bits");
-}
-
-int hnd_roundtrip_f16(float* x, int64_t numel, void* stream) {
-  HND_REQUIRE(x && numel > 0, "hnd_roundtrip_f16: bad arguments");
-  hipLaunchKernelGGL(roundtrip_f16_kernel, dim3(grid_for(numel)), dim3(256), 0, hnd::as_stream(stream), x,
-                     (long long)numel);
-  return hnd::check_launch("hnd_roundtrip_f16");
 }
 
 int hnd_fill(float* x, int64_t numel, float value, void* stream) {

@@ -1,9 +1,10 @@
 // include/hnd_entropy.h: the entropy-coded link payload of the bottleneck codec -- a canonical, length-limited Huffman code
 // over the quantiser's codes in independently decodable chunks of 256 symbols.  The format is the header's; this file is
 // the histogram, the three launches of the encoder and the one launch of the decoder.  Byte work and, in the decoder, the
-// fp32 sequence of unpack_dequantize_kernel (csrc/elementwise.hip): the file is built without FMA contraction.
+// dequantise of csrc/quant_math.h, whose contract has the file built without FMA contraction.
 #include "common.h"
 #include "hnd_entropy.h"
+#include "quant_math.h"
 
 namespace {
 
@@ -75,15 +76,10 @@ __device__ __forceinline__ int gather4(const uint8_t* __restrict__ q, unsigned i
                                        int cs, unsigned sym[4]) {
   if (i0 >= numel) return 0;
   const int count = numel - i0 < 4u ? (int)(numel - i0) : 4;
-  unsigned plane = i0 / hw, pix = i0 - plane * hw;                 // plane = img * c + ch
-  unsigned img = plane / (unsigned)c;
-  int ch = (int)(plane - img * (unsigned)c);
+  hnd::quant::NchwWalk<unsigned> at(i0, hw, c);
   for (int k = 0; k < count; ++k) {
-    sym[k] = q[((unsigned long long)img * hw + pix) * cs + ch];
-    if (++pix == hw) {
-      pix = 0;
-      if (++ch == c) { ch = 0; ++img; }
-    }
+    sym[k] = q[at.offset(cs)];
+    at.next();
   }
   return count;
 }
@@ -231,7 +227,6 @@ __global__ void __launch_bounds__(256) decode_dequantize_kernel(const uint8_t* _
                                                                 const unsigned* __restrict__ offsets, const DecTable tab,
                                                                 const float* __restrict__ qp, float* __restrict__ x,
                                                                 unsigned hw, int c, int cs, unsigned tiles) {
-#pragma clang fp contract(off)
   __shared__ uint16_t lut[kLut];
   __shared__ unsigned stage[kGroup * kTileChunks * kSlotDwords];
   for (unsigned e = threadIdx.x; e < (unsigned)kLut; e += 256) {    // canonical decoding of every 12-bit window
@@ -293,7 +288,7 @@ __global__ void __launch_bounds__(256) decode_dequantize_kernel(const uint8_t* _
         if (ch < c) {
           const unsigned s0 = (img * (unsigned)c + ch) * hw + p0, s = s0 + pix;
           const unsigned slot = (unsigned)(ch - g0) * kTileChunks + ((s >> 8) - (s0 >> 8));
-          out[e] = __fmul_rn(scale, __fsub_rn((float)sb[slot * (kSlotDwords * 4) + (s & 255u)], zp));   // scale * (q - zero_point)
+          out[e] = hnd::quant::dequantize_one((float)sb[slot * (kSlotDwords * 4) + (s & 255u)], scale, zp);
         }
       }
       float4 v4 = make_float4(out[0], out[1], out[2], out[3]);

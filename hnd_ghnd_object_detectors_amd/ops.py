@@ -733,6 +733,98 @@ def minmax_scratch_elems():
     return _L.hnd_minmax_scratch_elems()
 
 
+# ---- the argument checks of the quantiser wrappers below (codec, fake quantiser, fixed range, entropy coder, per channel).
+# One set; `flavour` picks the texts, which every family keeps as its callers know them: 'range' (include/hnd_qrange.h),
+# 'entropy' (include/hnd_entropy.h) or 'channel' (include/hnd_qchannel.h).  All raise ValueError; the codec and the batch
+# fake quantiser assert their buffers as they always have.
+def _q_bits(who, bits):
+    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
+        raise ValueError('%s: bits=%r outside 1 ... 8' % (who, bits))
+    return bits
+
+
+def _q_geometry(who, x, c, flavour='range', dtype=torch.float32):
+    """(npix, cs) of the NHWC buffer x with c real channels"""
+    dims_ok = isinstance(x, torch.Tensor) and (x.dim() == 4 if flavour == 'entropy' else x.dim() >= 1)
+    if not (dims_ok and x.dtype == dtype and x.is_contiguous()):
+        raise ValueError('%s: needs a contiguous %s' % (who, {
+            'range': 'fp32 NHWC buffer', 'entropy': '%s NHWC buffer [N, H, W, cs]' % dtype,
+            'channel': '%s NHWC buffer' % str(dtype).replace('torch.', '')}[flavour]))
+    cs = x.shape[-1]
+    cmax = min(cs, QCHANNEL_MAX_C) if flavour == 'channel' else cs
+    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cmax or cs % 4 or x.numel() == 0:
+        raise ValueError('%s: c=%r real channels in a pixel stride of %d%s' % (who, c, cs, {
+            'range': ' floats (0 < c <= stride, stride % 4 == 0)', 'entropy': ' (0 < c <= stride, stride % 4 == 0)',
+            'channel': ' floats (0 < c <= stride, c <= %d, stride %% 4 == 0)' % QCHANNEL_MAX_C}[flavour]))
+    return x.numel() // cs, cs
+
+
+def _q_nhwc(who, x, flavour):
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
+        raise ValueError('%s: %s' % (who, 'needs the NHWC buffer [N, H, W, cs]' if flavour == 'channel' else
+                                     'x must be [N, H, W, cs]'))
+    return x.shape
+
+
+def _q_qparams(who, qparams, c=None):
+    """per tensor (c None): at least the 4 values; per channel: exactly [c, 4]"""
+    ok = isinstance(qparams, torch.Tensor) and qparams.dtype == torch.float32 and qparams.is_contiguous()
+    if not (ok and (qparams.numel() >= 4 if c is None else qparams.numel() == 4 * c)):
+        raise ValueError('%s: qparams must be a contiguous fp32 tensor %s' % (who, 'of 4 values' if c is None else '[%d, 4]' % c))
+    return qparams
+
+
+def _q_scratch(who, scratch, cs=None):
+    """per tensor (cs None): minmax_scratch_elems() floats; per channel: qchannel_scratch_elems(cs), a contiguous tensor"""
+    if cs is None:
+        if not (scratch.dtype == torch.float32 and scratch.numel() >= minmax_scratch_elems()):
+            raise ValueError('%s: scratch must hold minmax_scratch_elems() floats' % who)
+    elif not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float32 and scratch.is_contiguous()
+              and scratch.numel() >= qchannel_scratch_elems(cs)):
+        raise ValueError('%s: scratch must be a contiguous fp32 buffer of qchannel_scratch_elems(%d) = %d floats'
+                         % (who, cs, qchannel_scratch_elems(cs)))
+    return scratch
+
+
+def _q_payload(who, payload, x, c, bits, flavour='range'):
+    """the bit-packed payload of the c real channels of x [N, H, W, cs]: exactly codec_packed_bytes uint8 bytes"""
+    n, h, w, _ = x.shape
+    numel, nbytes = n * c * h * w, codec_packed_bytes(n * c * h * w, bits)
+    if not ((flavour != 'channel' or isinstance(payload, torch.Tensor)) and payload.dtype == torch.uint8
+            and payload.is_contiguous() and payload.numel() == nbytes > 0):
+        raise ValueError('%s: payload must be %s' % (who, '%d uint8 bytes' % nbytes if flavour != 'channel' else
+                                                     'a contiguous uint8 buffer of codec_packed_bytes(%d, %d) = %d bytes'
+                                                     % (numel, bits, nbytes)))
+    return payload
+
+
+# `strict` in the three checkers below: the per-channel wrappers (and qrange_mask_grad) answer a non-tensor with their
+# ValueError; the fixed-range wrappers never tested for one and let the attribute access fail.  Callers see either, so
+# both stay.
+def _q_like(who, name, t, x, dtype, strict):
+    """`name` is a contiguous buffer of x's extent: a float destination (`out`) has x's shape, a byte destination (`q`)
+    x's element count -- the codes are handed on flat as well as shaped"""
+    same = (lambda: tuple(t.shape) == tuple(x.shape)) if dtype == torch.float32 else (lambda: t.numel() == x.numel())
+    if not ((not strict or isinstance(t, torch.Tensor)) and t.dtype == dtype and t.is_contiguous() and same()):
+        raise ValueError('%s: %s must be a contiguous %s buffer of x\'s shape'
+                         % (who, name, 'fp32' if dtype == torch.float32 else 'uint8'))
+    return t
+
+
+def _q_stats(who, stats, npix, cs, strict):
+    if stats is not None and not ((not strict or isinstance(stats, torch.Tensor)) and stats.dtype == torch.float32
+                                  and stats.is_contiguous() and stats.numel() == fake_quantize_tiles(npix) * 2 * cs):
+        raise ValueError('%s: stats must be a contiguous fp32 buffer [%d, 2, %d]' % (who, fake_quantize_tiles(npix), cs))
+    return stats
+
+
+def _q_mask(who, mask, npix, cs, strict):
+    if not ((not strict or isinstance(mask, torch.Tensor)) and mask.dtype == torch.uint8 and mask.is_contiguous()
+            and mask.numel() == npix * (cs // 4)):
+        raise ValueError('%s: mask must be a contiguous uint8 buffer of %d bytes' % (who, npix * (cs // 4)))
+    return mask
+
+
 # include/hnd_codec.h: the codec at 1 ... 8 bits.  x is the NHWC fp32 buffer [N, H, W, cs] with c real channels.
 def codec_packed_bytes(numel, bits):
     """bytes of the bit-packed payload of `numel` values at `bits` bits each: ceil(numel * bits / 8); 0 for bad arguments"""
@@ -747,21 +839,24 @@ def quantize_bits(x, c, bits, q, qparams, scratch):
                                stream_ptr()), 'hnd_quantize_bits')
 
 
-def quantize_pack_bits(x, c, bits, payload, qparams, scratch):
-    """quantise the c real channels of x and pack them, in logical NCHW order, LSB first, into the 1-D uint8 `payload` of
-    exactly codec_packed_bytes(N * c * H * W, bits) bytes (format: include/hnd_codec.h)"""
+def _assert_payload(payload, x, c, bits):
     n, h, w, cs = x.shape
     assert payload.dtype == torch.uint8 and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0, \
         (tuple(payload.shape), (n, c, h, w), bits)
+    return n, h, w, cs
+
+
+def quantize_pack_bits(x, c, bits, payload, qparams, scratch):
+    """quantise the c real channels of x and pack them, in logical NCHW order, LSB first, into the 1-D uint8 `payload` of
+    exactly codec_packed_bytes(N * c * H * W, bits) bytes (format: include/hnd_codec.h)"""
+    n, h, w, cs = _assert_payload(payload, x, c, bits)
     check(_L.hnd_quantize_pack_bits(ptr(x), n, h, w, c, cs, int(bits), ptr(payload), ptr(qparams), ptr(scratch),
                                     stream_ptr()), 'hnd_quantize_pack_bits')
 
 
 def unpack_dequantize_bits(payload, qparams, x, c, bits):
     """the inverse: scale * (q - zero_point) into the c real channels of x [N, H, W, cs], 0 into its pad channels"""
-    n, h, w, cs = x.shape
-    assert payload.dtype == torch.uint8 and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0, \
-        (tuple(payload.shape), (n, c, h, w), bits)
+    n, h, w, cs = _assert_payload(payload, x, c, bits)
     check(_L.hnd_unpack_dequantize_bits(ptr(payload), ptr(qparams), ptr(x), n, h, w, c, cs, int(bits), stream_ptr()),
           'hnd_unpack_dequantize_bits')
 
@@ -777,8 +872,7 @@ def fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None):
     dequantize_u8(quantize_bits(x)) -- into `out` (default: in place), 0 into the pad channels; `stats`
     [fake_quantize_tiles(npix), 2, cs] receives the per-tile (sum, sum of squares) of what was stored, for bn_finalize.
     Returns the destination."""
-    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
-        raise ValueError('fake_quantize_bits: bits=%r outside 1 ... 8' % (bits,))
+    _q_bits('fake_quantize_bits', bits)
     cs = x.shape[-1]
     npix = x.numel() // cs
     out = x if out is None else out
@@ -798,43 +892,18 @@ def qrange_abi():
     return int(_L.hnd_qrange_abi())
 
 
-def _qrange_bits(who, bits):
-    if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
-        raise ValueError('%s: bits=%r outside 1 ... 8' % (who, bits))
-    return bits
-
-
-def _qrange_geometry(who, x, c):
-    """(npix, cs) of the NHWC fp32 buffer x with c real channels"""
-    if not (isinstance(x, torch.Tensor) and x.dtype == torch.float32 and x.dim() >= 1 and x.is_contiguous()):
-        raise ValueError('%s: needs a contiguous fp32 NHWC buffer' % who)
-    cs = x.shape[-1]
-    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cs or cs % 4 or x.numel() == 0:
-        raise ValueError('%s: c=%r real channels in a pixel stride of %d floats (0 < c <= stride, stride %% 4 == 0)'
-                         % (who, c, cs))
-    return x.numel() // cs, cs
-
-
-def _qrange_qparams(who, qparams):
-    if not (isinstance(qparams, torch.Tensor) and qparams.dtype == torch.float32 and qparams.numel() >= 4
-            and qparams.is_contiguous()):
-        raise ValueError('%s: qparams must be a contiguous fp32 tensor of 4 values' % who)
-    return qparams
-
-
 def qrange_observe(x, c, bits, momentum, state, qparams, scratch):
     """fold the batch min / max of the c real channels of x into state = {running_min, running_max, steps, 0} (the first
     call initialises, then running += momentum * (batch - running)) and write qparams of the running pair at `bits` bits"""
     who = 'qrange_observe'
-    _qrange_bits(who, bits)
-    npix, cs = _qrange_geometry(who, x, c)
+    _q_bits(who, bits)
+    npix, cs = _q_geometry(who, x, c)
     if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0 < momentum <= 1:
         raise ValueError('%s: momentum=%r outside (0, 1]' % (who, momentum))
-    _qrange_qparams(who, qparams)
+    _q_qparams(who, qparams)
     if not (state.dtype == torch.float32 and state.numel() == 4 and state.is_contiguous()):
         raise ValueError('%s: state must be a contiguous fp32 tensor of 4 values' % who)
-    if not (scratch.dtype == torch.float32 and scratch.numel() >= minmax_scratch_elems()):
-        raise ValueError('%s: scratch must hold minmax_scratch_elems() floats' % who)
+    _q_scratch(who, scratch)
     check(_L.hnd_qrange_observe(ptr(x), npix, c, cs, float(momentum), bits, ptr(state), ptr(qparams), ptr(scratch),
                                 stream_ptr()), 'hnd_qrange_observe')
 
@@ -842,14 +911,14 @@ def qrange_observe(x, c, bits, momentum, state, qparams, scratch):
 def qrange_qparams(lo, hi, bits, qparams):
     """qparams of the literal range [lo, hi] at `bits` bits, computed on the device with the codec's formula"""
     who = 'qrange_qparams'
-    _qrange_bits(who, bits)
+    _q_bits(who, bits)
     try:
         lo, hi = float(lo), float(hi)
     except (TypeError, ValueError):
         raise ValueError('%s: the range (%r, %r) is not a pair of numbers' % (who, lo, hi))
     if not (math.isfinite(lo) and math.isfinite(hi) and lo < hi):
         raise ValueError('%s: the range needs finite lo < hi, got (%r, %r)' % (who, lo, hi))
-    _qrange_qparams(who, qparams)
+    _q_qparams(who, qparams)
     check(_L.hnd_qrange_qparams(lo, hi, bits, ptr(qparams), stream_ptr()), 'hnd_qrange_qparams')
     return qparams
 
@@ -864,17 +933,13 @@ def fake_quantize_range(x, c, bits, qparams, out=None, mask=None, stats=None):
     end codes; `mask` (uint8, qrange_mask_shape(x)) receives bit k of byte g = channel 4 g + k was not clipped.  Returns
     the destination."""
     who = 'fake_quantize_range'
-    _qrange_bits(who, bits)
-    npix, cs = _qrange_geometry(who, x, c)
-    _qrange_qparams(who, qparams)
-    out = x if out is None else out
-    if not (out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == tuple(x.shape)):
-        raise ValueError('%s: out must be a contiguous fp32 buffer of x\'s shape' % who)
-    if mask is not None and not (mask.dtype == torch.uint8 and mask.is_contiguous() and mask.numel() == npix * (cs // 4)):
-        raise ValueError('%s: mask must be a contiguous uint8 buffer of %d bytes' % (who, npix * (cs // 4)))
-    if stats is not None and not (stats.dtype == torch.float32 and stats.is_contiguous()
-                                  and stats.numel() == fake_quantize_tiles(npix) * 2 * cs):
-        raise ValueError('%s: stats must be a contiguous fp32 buffer [%d, 2, %d]' % (who, fake_quantize_tiles(npix), cs))
+    _q_bits(who, bits)
+    npix, cs = _q_geometry(who, x, c)
+    _q_qparams(who, qparams)
+    out = _q_like(who, 'out', x if out is None else out, x, torch.float32, False)
+    if mask is not None:
+        _q_mask(who, mask, npix, cs, False)
+    _q_stats(who, stats, npix, cs, False)
     check(_L.hnd_fake_quantize_range(ptr(x), ptr(out), npix, c, cs, bits, ptr(qparams), ptr(mask), ptr(stats),
                                      stream_ptr()), 'hnd_fake_quantize_range')
     return out
@@ -883,10 +948,8 @@ def fake_quantize_range(x, c, bits, qparams, out=None, mask=None, stats=None):
 def qrange_mask_grad(g, mask, c):
     """in place: +0 into the real channels of g whose mask bit is 0 (the backward of fake_quantize_range's clipping)"""
     who = 'qrange_mask_grad'
-    npix, cs = _qrange_geometry(who, g, c)
-    if not (isinstance(mask, torch.Tensor) and mask.dtype == torch.uint8 and mask.is_contiguous()
-            and mask.numel() == npix * (cs // 4)):
-        raise ValueError('%s: mask must be a contiguous uint8 buffer of %d bytes' % (who, npix * (cs // 4)))
+    npix, cs = _q_geometry(who, g, c)
+    _q_mask(who, mask, npix, cs, True)
     check(_L.hnd_qrange_mask_grad(ptr(g), ptr(mask), npix, c, cs, stream_ptr()), 'hnd_qrange_mask_grad')
     return g
 
@@ -894,11 +957,10 @@ def qrange_mask_grad(g, mask, c):
 def quantize_range_bits(x, c, bits, q, qparams):
     """quantize_bits on the fixed range of `qparams` (read, not written): one launch"""
     who = 'quantize_range_bits'
-    _qrange_bits(who, bits)
-    npix, cs = _qrange_geometry(who, x, c)
-    _qrange_qparams(who, qparams)
-    if not (q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
-        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
+    _q_bits(who, bits)
+    npix, cs = _q_geometry(who, x, c)
+    _q_qparams(who, qparams)
+    _q_like(who, 'q', q, x, torch.uint8, False)
     check(_L.hnd_quantize_range_bits(ptr(x), npix, c, cs, bits, ptr(q), ptr(qparams), stream_ptr()),
           'hnd_quantize_range_bits')
 
@@ -906,15 +968,11 @@ def quantize_range_bits(x, c, bits, q, qparams):
 def quantize_pack_range_bits(x, c, bits, payload, qparams):
     """quantize_pack_bits on the fixed range of `qparams` (read, not written): one launch"""
     who = 'quantize_pack_range_bits'
-    _qrange_bits(who, bits)
-    _qrange_geometry(who, x, c)
-    _qrange_qparams(who, qparams)
-    if x.dim() != 4:
-        raise ValueError('%s: x must be [N, H, W, cs]' % who)
-    n, h, w, cs = x.shape
-    if not (payload.dtype == torch.uint8 and payload.is_contiguous()
-            and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0):
-        raise ValueError('%s: payload must be %d uint8 bytes' % (who, codec_packed_bytes(n * c * h * w, bits)))
+    _q_bits(who, bits)
+    _q_geometry(who, x, c)
+    _q_qparams(who, qparams)
+    n, h, w, cs = _q_nhwc(who, x, 'range')
+    _q_payload(who, payload, x, c, bits)
     check(_L.hnd_quantize_pack_range_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload), ptr(qparams), stream_ptr()),
           'hnd_quantize_pack_range_bits')
 
@@ -942,12 +1000,9 @@ def entropy_scratch_bytes(numel):
 
 
 def _entropy_geometry(who, t, c, bits, dtype):
-    _qrange_bits(who, bits)
-    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.dim() == 4 and t.is_contiguous()):
-        raise ValueError('%s: needs a contiguous %s NHWC buffer [N, H, W, cs]' % (who, dtype))
+    _q_bits(who, bits)
+    _q_geometry(who, t, c, 'entropy', dtype)
     n, h, w, cs = t.shape
-    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cs or cs % 4 or t.numel() == 0:
-        raise ValueError('%s: c=%r real channels in a pixel stride of %d (0 < c <= stride, stride %% 4 == 0)' % (who, c, cs))
     if entropy_chunks(n * c * h * w) == 0:
         raise ValueError('%s: %d values are more than the 2^30 one stream holds' % (who, n * c * h * w))
     return n, h, w, cs
@@ -998,7 +1053,7 @@ def entropy_decode_dequantize(payload, offsets, lengths, qparams, x, c, bits):
     who = 'entropy_decode_dequantize'
     n, h, w, cs = _entropy_geometry(who, x, c, bits, torch.float32)
     lengths = _entropy_lengths(who, lengths, bits)
-    _qrange_qparams(who, qparams)
+    _q_qparams(who, qparams)
     if not (payload.dtype == torch.uint8 and payload.is_contiguous() and payload.numel() > 0):
         raise ValueError('%s: payload must be a non-empty contiguous uint8 buffer' % who)
     _entropy_words(who, offsets, 'offsets', entropy_chunks(n * c * h * w) + 1)
@@ -1020,60 +1075,22 @@ def qchannel_scratch_elems(cs):
     return int(_L.hnd_qchannel_scratch_elems(int(cs)))
 
 
-def _qchannel_geometry(who, x, c, bits, dtype=torch.float32):
-    """(npix, cs) of the NHWC buffer x with c real channels, after the argument checks every per-channel wrapper shares"""
-    _qrange_bits(who, bits)
-    if not (isinstance(x, torch.Tensor) and x.dtype == dtype and x.dim() >= 1 and x.is_contiguous()):
-        raise ValueError('%s: needs a contiguous %s NHWC buffer' % (who, str(dtype).replace('torch.', '')))
-    cs = x.shape[-1]
-    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= min(cs, QCHANNEL_MAX_C) or cs % 4 or x.numel() == 0:
-        raise ValueError('%s: c=%r real channels in a pixel stride of %d floats (0 < c <= stride, c <= %d, stride %% 4 == 0)'
-                         % (who, c, cs, QCHANNEL_MAX_C))
-    return x.numel() // cs, cs
-
-
-def _qchannel_qparams(who, qparams, c):
-    if not (isinstance(qparams, torch.Tensor) and qparams.dtype == torch.float32 and qparams.numel() == 4 * c
-            and qparams.is_contiguous()):
-        raise ValueError('%s: qparams must be a contiguous fp32 tensor [%d, 4]' % (who, c))
-    return qparams
-
-
-def _qchannel_scratch(who, scratch, cs):
-    if not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float32 and scratch.is_contiguous()
-            and scratch.numel() >= qchannel_scratch_elems(cs)):
-        raise ValueError('%s: scratch must be a contiguous fp32 buffer of qchannel_scratch_elems(%d) = %d floats'
-                         % (who, cs, qchannel_scratch_elems(cs)))
-    return scratch
-
-
-def _qchannel_payload(who, payload, x, c, bits):
-    n, h, w, _ = x.shape
-    if not (isinstance(payload, torch.Tensor) and payload.dtype == torch.uint8 and payload.is_contiguous()
-            and payload.numel() == codec_packed_bytes(n * c * h * w, bits) > 0):
-        raise ValueError('%s: payload must be a contiguous uint8 buffer of codec_packed_bytes(%d, %d) = %d bytes'
-                         % (who, n * c * h * w, bits, codec_packed_bytes(n * c * h * w, bits)))
-    return n, h, w
-
-
 def qchannel_quantize_bits(x, c, bits, q, qparams, scratch):
     """quantize_bits with the range of every channel its own: one value per byte into q (uint8, x's shape), pad channels 0"""
     who = 'qchannel_quantize_bits'
-    npix, cs = _qchannel_geometry(who, x, c, bits)
-    if not (isinstance(q, torch.Tensor) and q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
-        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
-    check(_L.hnd_qchannel_quantize_bits(ptr(x), npix, c, cs, bits, ptr(q), ptr(_qchannel_qparams(who, qparams, c)),
-                                        ptr(_qchannel_scratch(who, scratch, cs)), stream_ptr()),
-          'hnd_qchannel_quantize_bits')
+    _q_bits(who, bits)
+    npix, cs = _q_geometry(who, x, c, 'channel')
+    _q_like(who, 'q', q, x, torch.uint8, True)
+    check(_L.hnd_qchannel_quantize_bits(ptr(x), npix, c, cs, bits, ptr(q), ptr(_q_qparams(who, qparams, c)),
+                                        ptr(_q_scratch(who, scratch, cs)), stream_ptr()), 'hnd_qchannel_quantize_bits')
 
 
 def qchannel_dequantize_u8(q, qparams, x, c):
     """the inverse: scale[ch] * (q - zero_point[ch]) into the c real channels of x, 0 into its pad channels"""
     who = 'qchannel_dequantize_u8'
-    npix, cs = _qchannel_geometry(who, x, c, 8)
-    if not (isinstance(q, torch.Tensor) and q.dtype == torch.uint8 and q.is_contiguous() and q.numel() == x.numel()):
-        raise ValueError('%s: q must be a contiguous uint8 buffer of x\'s shape' % who)
-    check(_L.hnd_qchannel_dequantize_u8(ptr(q), ptr(_qchannel_qparams(who, qparams, c)), ptr(x), npix, c, cs, stream_ptr()),
+    npix, cs = _q_geometry(who, x, c, 'channel')
+    _q_like(who, 'q', q, x, torch.uint8, True)
+    check(_L.hnd_qchannel_dequantize_u8(ptr(q), ptr(_q_qparams(who, qparams, c)), ptr(x), npix, c, cs, stream_ptr()),
           'hnd_qchannel_dequantize_u8')
     return x
 
@@ -1081,25 +1098,24 @@ def qchannel_dequantize_u8(q, qparams, x, c):
 def qchannel_quantize_pack_bits(x, c, bits, payload, qparams, scratch):
     """quantize_pack_bits with the range of every channel its own: the payload format is that of include/hnd_codec.h"""
     who = 'qchannel_quantize_pack_bits'
-    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
-        raise ValueError('%s: needs the NHWC buffer [N, H, W, cs]' % who)
-    _, cs = _qchannel_geometry(who, x, c, bits)
-    n, h, w = _qchannel_payload(who, payload, x, c, bits)
-    check(_L.hnd_qchannel_quantize_pack_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload),
-                                             ptr(_qchannel_qparams(who, qparams, c)),
-                                             ptr(_qchannel_scratch(who, scratch, cs)), stream_ptr()),
+    n, h, w, cs = _q_nhwc(who, x, 'channel')
+    _q_bits(who, bits)
+    _q_geometry(who, x, c, 'channel')
+    _q_payload(who, payload, x, c, bits, 'channel')
+    check(_L.hnd_qchannel_quantize_pack_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload), ptr(_q_qparams(who, qparams, c)),
+                                             ptr(_q_scratch(who, scratch, cs)), stream_ptr()),
           'hnd_qchannel_quantize_pack_bits')
 
 
 def qchannel_unpack_dequantize_bits(payload, qparams, x, c, bits):
     """the inverse: scale[ch] * (q - zero_point[ch]) into the c real channels of x [N, H, W, cs], 0 into its pad channels"""
     who = 'qchannel_unpack_dequantize_bits'
-    if not (isinstance(x, torch.Tensor) and x.dim() == 4):
-        raise ValueError('%s: needs the NHWC buffer [N, H, W, cs]' % who)
-    _, cs = _qchannel_geometry(who, x, c, bits)
-    n, h, w = _qchannel_payload(who, payload, x, c, bits)
-    check(_L.hnd_qchannel_unpack_dequantize_bits(ptr(payload), ptr(_qchannel_qparams(who, qparams, c)), ptr(x), n, h, w, c,
-                                                 cs, bits, stream_ptr()), 'hnd_qchannel_unpack_dequantize_bits')
+    n, h, w, cs = _q_nhwc(who, x, 'channel')
+    _q_bits(who, bits)
+    _q_geometry(who, x, c, 'channel')
+    _q_payload(who, payload, x, c, bits, 'channel')
+    check(_L.hnd_qchannel_unpack_dequantize_bits(ptr(payload), ptr(_q_qparams(who, qparams, c)), ptr(x), n, h, w, c, cs,
+                                                 bits, stream_ptr()), 'hnd_qchannel_unpack_dequantize_bits')
     return x
 
 
@@ -1109,16 +1125,12 @@ def qchannel_fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=No
     [fake_quantize_tiles(npix), 2, cs] receives the per-tile (sum, sum of squares) of what was stored, for bn_finalize.
     Returns the destination."""
     who = 'qchannel_fake_quantize_bits'
-    npix, cs = _qchannel_geometry(who, x, c, bits)
-    out = x if out is None else out
-    if not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.is_contiguous()
-            and tuple(out.shape) == tuple(x.shape)):
-        raise ValueError('%s: out must be a contiguous fp32 buffer of x\'s shape' % who)
-    if stats is not None and not (isinstance(stats, torch.Tensor) and stats.dtype == torch.float32 and stats.is_contiguous()
-                                  and stats.numel() == fake_quantize_tiles(npix) * 2 * cs):
-        raise ValueError('%s: stats must be a contiguous fp32 buffer [%d, 2, %d]' % (who, fake_quantize_tiles(npix), cs))
-    check(_L.hnd_qchannel_fake_quantize_bits(ptr(x), ptr(out), npix, c, cs, bits, ptr(_qchannel_qparams(who, qparams, c)),
-                                             ptr(_qchannel_scratch(who, scratch, cs)), ptr(stats), stream_ptr()),
+    _q_bits(who, bits)
+    npix, cs = _q_geometry(who, x, c, 'channel')
+    out = _q_like(who, 'out', x if out is None else out, x, torch.float32, True)
+    _q_stats(who, stats, npix, cs, True)
+    check(_L.hnd_qchannel_fake_quantize_bits(ptr(x), ptr(out), npix, c, cs, bits, ptr(_q_qparams(who, qparams, c)),
+                                             ptr(_q_scratch(who, scratch, cs)), ptr(stats), stream_ptr()),
           'hnd_qchannel_fake_quantize_bits')
     return out
 

@@ -546,35 +546,34 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
                                torch.empty(ops.qchannel_scratch_elems(cs) if self.per_channel else
                                            ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         q, qparams, scratch = self._bufs[key]
-        if self.per_channel:                # a scale and a zero point per channel (include/hnd_qchannel.h)
-            if self.packed:
-                ops.qchannel_quantize_pack_bits(buf, c, self.num_bits, q, qparams, scratch)
-                return PackedBottleneck(q, z.shape, self.num_bits, qparams, origin=buf, per_channel=True), target
-            ops.qchannel_quantize_bits(buf, c, self.num_bits, q, qparams, scratch)
-            qt = q[..., :c].permute(0, 3, 1, 2)
-            return QuantizedTensor(attach(qt, q), qparams[:, 2], qparams[:, 3], qparams, origin=buf, channels=c,
-                                   per_channel=True, num_bits=self.num_bits), target
-        fixed = self._static_qparams_on(buf.device)
-        if fixed is not None:               # one launch on the fixed range (include/hnd_qrange.h)
-            if self.packed:
-                ops.quantize_pack_range_bits(buf, c, self.num_bits, q, fixed)
-                return PackedBottleneck(q, z.shape, self.num_bits, fixed, origin=buf), target
-            ops.quantize_range_bits(buf, c, self.num_bits, q, fixed)
-            if self.entropy:
-                return self._entropy_code(q, c, fixed, z.shape, buf), target
-            qt = q[..., :c].permute(0, 3, 1, 2)
-            return QuantizedTensor(attach(qt, q), fixed[2], fixed[3], fixed, origin=buf, channels=c), target
+        bits, per_channel = self.num_bits, self.per_channel
+        fixed = None if per_channel else self._static_qparams_on(buf.device)
+        # per flavour: the packing call, the one-value-per-byte call (closures: their argument lists differ; one of the two
+        # runs) and the qparams the result carries
+        if per_channel:                     # a scale and a zero point per channel (include/hnd_qchannel.h)
+            qp = qparams
+            pack = lambda: ops.qchannel_quantize_pack_bits(buf, c, bits, q, qp, scratch)
+            plain = lambda: ops.qchannel_quantize_bits(buf, c, bits, q, qp, scratch)
+        elif fixed is not None:             # one launch on the fixed range (include/hnd_qrange.h)
+            qp = fixed
+            pack = lambda: ops.quantize_pack_range_bits(buf, c, bits, q, qp)
+            plain = lambda: ops.quantize_range_bits(buf, c, bits, q, qp)
+        else:                               # min / max of this tensor
+            qp = qparams
+            pack = lambda: ops.quantize_pack_bits(buf, c, bits, q, qp, scratch)
+            plain = lambda: ops.quantize_u8(buf, c, q, qp, scratch) if bits == 8 else \
+                ops.quantize_bits(buf, c, bits, q, qp, scratch)
         if self.packed:
-            ops.quantize_pack_bits(buf, c, self.num_bits, q, qparams, scratch)
-            return PackedBottleneck(q, z.shape, self.num_bits, qparams, origin=buf), target
-        if self.num_bits == 8:
-            ops.quantize_u8(buf, c, q, qparams, scratch)
-        else:
-            ops.quantize_bits(buf, c, self.num_bits, q, qparams, scratch)
-        if self.entropy:
-            return self._entropy_code(q, c, qparams, z.shape, buf), target
+            pack()
+            return PackedBottleneck(q, z.shape, bits, qp, origin=buf, per_channel=per_channel), target
+        plain()
+        if self.entropy:                    # never per channel: _check_per_channel_combination refuses the pair by name
+            assert not per_channel
+            return self._entropy_code(q, c, qp, z.shape, buf), target
         qt = q[..., :c].permute(0, 3, 1, 2)
-        return QuantizedTensor(attach(qt, q), qparams[2], qparams[3], qparams, origin=buf, channels=c), target
+        scale, zero_point = (qp[:, 2], qp[:, 3]) if per_channel else (qp[2], qp[3])
+        return QuantizedTensor(attach(qt, q), scale, zero_point, qp, origin=buf, channels=c, per_channel=per_channel,
+                               num_bits=bits if per_channel else None), target
 
 
 class Dequantizer(object):
@@ -656,30 +655,22 @@ class FakeQuantizer(_StaticRange):
     def __call__(self, z, target):
         self._check_resolved()
         buf = to_nhwc(z)                    # [N, H, W, cs] fp32 bottleneck (pad channels are 0)
-        fixed = self._static_qparams_on(buf.device)
-        if fixed is not None:
+        c, cs, dev = z.shape[1], buf.shape[-1], buf.device
+        fixed = self._static_qparams_on(dev)
+        if fixed is not None:               # one launch on the fixed range (include/hnd_qrange.h)
             self.qparams = fixed
-            ops.fake_quantize_range(buf, z.shape[1], self.num_bits, fixed)
-            if getattr(z, '_hnd', None) is buf:
-                return z, target
-            return attach(buf[..., :z.shape[1]].permute(0, 3, 1, 2), buf), target
-        c = z.shape[1]
-        if self.per_channel:                # a scale and a zero point per channel (include/hnd_qchannel.h)
-            key = (buf.device, c, buf.shape[-1])
+            ops.fake_quantize_range(buf, c, self.num_bits, fixed)
+        else:
+            # per flavour: the call, the key of its two buffers, the shape of qparams and the floats of scratch
+            if self.per_channel:            # a scale and a zero point per channel (include/hnd_qchannel.h)
+                call, key, qshape, nscratch = ops.qchannel_fake_quantize_bits, (dev, c, cs), (c, 4), ops.qchannel_scratch_elems
+            else:
+                call, key, qshape, nscratch = ops.fake_quantize_bits, dev, (4,), lambda cs: ops.minmax_scratch_elems()
             if key not in self._bufs:
-                self._bufs[key] = (torch.empty((c, 4), dtype=torch.float32, device=buf.device),
-                                   torch.empty(ops.qchannel_scratch_elems(buf.shape[-1]), dtype=torch.float32,
-                                               device=buf.device))
+                self._bufs[key] = (torch.empty(qshape, dtype=torch.float32, device=dev),
+                                   torch.empty(nscratch(cs), dtype=torch.float32, device=dev))
             self.qparams, scratch = self._bufs[key]
-            ops.qchannel_fake_quantize_bits(buf, c, self.num_bits, self.qparams, scratch)
-            if getattr(z, '_hnd', None) is buf:
-                return z, target
-            return attach(buf[..., :c].permute(0, 3, 1, 2), buf), target
-        if buf.device not in self._bufs:
-            self._bufs[buf.device] = (torch.empty(4, dtype=torch.float32, device=buf.device),
-                                      torch.empty(ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
-        self.qparams, scratch = self._bufs[buf.device]
-        ops.fake_quantize_bits(buf, c, self.num_bits, self.qparams, scratch)
+            call(buf, c, self.num_bits, self.qparams, scratch)
         if getattr(z, '_hnd', None) is buf:         # a HIP-path tensor: a view of the buffer just rewritten
             return z, target
         return attach(buf[..., :c].permute(0, 3, 1, 2), buf), target
