@@ -1,7 +1,7 @@
 """ctypes binding of libhnd_hip.so, derived from its C headers: include/hnd_hip.h, hnd_optim.h (the further optimizer
 kinds), hnd_codec.h (the 1 ... 8-bit bottleneck codec) and hnd_qat.h (the fake-quantised bottleneck of the training step),
 each with a version of its own, and -- beside those four -- hnd_qrange.h (the fixed quantisation range of the bottleneck)
-hnd_entropy.h (the entropy-coded link payload) and hnd_qchannel.h (per-channel scales), with versions of their own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
+hnd_entropy.h (the entropy-coded link payload), hnd_qchannel.h (per-channel scales) and hnd_qimage.h (per-image scales), with versions of their own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
 dictionaries, the ABI numbers, the symbol tuples and every restype / argtypes below come from what it read, so the headers
 are the only place the contract is written down.
 
@@ -165,6 +165,14 @@ QCHANNEL_MAX_C = QCHANNEL_HEADER.defines['HND_QCHANNEL_MAX_C']
 if QCHANNEL_HEADER.structs or QCHANNEL_HEADER.enums:
     raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % QCHANNEL_HEADER_NAME)
 
+# per-image scales for the codec and the fake quantiser: an eighth header, read as hnd_qrange.h is
+QIMAGE_HEADER_NAME = 'hnd_qimage.h'
+QIMAGE_HEADER = _read(QIMAGE_HEADER_NAME)
+QIMAGE_ABI, QIMAGE_SYMBOLS = QIMAGE_HEADER.defines['HND_QIMAGE_ABI'], tuple(sorted(QIMAGE_HEADER.functions))
+QIMAGE_MAX_N, QIMAGE_PART_BLOCKS = QIMAGE_HEADER.defines['HND_QIMAGE_MAX_N'], QIMAGE_HEADER.defines['HND_QIMAGE_PART_BLOCKS']
+if QIMAGE_HEADER.structs or QIMAGE_HEADER.enums:
+    raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % QIMAGE_HEADER_NAME)
+
 _lib = None
 
 
@@ -183,7 +191,7 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for header in list(HEADERS.values()) + [QRANGE_HEADER, ENTROPY_HEADER, QCHANNEL_HEADER]:
+    for header in list(HEADERS.values()) + [QRANGE_HEADER, ENTROPY_HEADER, QCHANNEL_HEADER, QIMAGE_HEADER]:
         for name, (res, args) in header.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -205,6 +213,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so entropy-coding ABI %d != expected %d' % (lib.hnd_entropy_abi(), ENTROPY_ABI))
     if lib.hnd_qchannel_abi() != QCHANNEL_ABI:
         raise HndLibraryError('libhnd_hip.so per-channel codec ABI %d != expected %d' % (lib.hnd_qchannel_abi(), QCHANNEL_ABI))
+    if lib.hnd_qimage_abi() != QIMAGE_ABI:
+        raise HndLibraryError('libhnd_hip.so per-image codec ABI %d != expected %d' % (lib.hnd_qimage_abi(), QIMAGE_ABI))
     _lib = lib
     return lib
 

@@ -28,12 +28,18 @@ def _fake_quantize_section(config):
     if section is None:
         return None, None, None
     shape = '{num_bits: b} or {num_bits: b, range: {type: batch}} or {num_bits: b, range: {type: ema, momentum: m}}' \
-            ' (each optionally with per_channel: true | false, not with range: {type: ema})'
+            ' (each optionally with per_channel: true | false or per_image: true | false, not both and neither with range: ' \
+            '{type: ema})'
     if not isinstance(section, dict) or 'num_bits' not in section or \
-            not set(section) <= {'num_bits', 'range', 'per_channel'}:
+            not set(section) <= {'num_bits', 'range', 'per_channel', 'per_image'}:
         raise ValueError('train.fake_quantize must be %s, got %r' % (shape, section))
     if not isinstance(section.get('per_channel', False), bool):
         raise ValueError('train.fake_quantize.per_channel=%r must be a bool' % (section['per_channel'],))
+    if not isinstance(section.get('per_image', False), bool):
+        raise ValueError('train.fake_quantize.per_image=%r must be a bool' % (section['per_image'],))
+    if section.get('per_image', False) and section.get('per_channel', False):
+        raise ValueError('train.fake_quantize: per_image together with per_channel is not built: the scales are per image or '
+                         'per channel')
     bits = section['num_bits']
     if isinstance(bits, bool) or not isinstance(bits, int) or not 1 <= bits <= 8:
         raise ValueError('train.fake_quantize.num_bits=%r is outside 1 ... 8, the widths the fake-quantised bottleneck '
@@ -51,6 +57,9 @@ def _fake_quantize_section(config):
             if section.get('per_channel', False):
                 raise ValueError('train.fake_quantize: per_channel together with range: {type: ema} is not built: the fixed '
                                  'range has no per-channel form (per-channel scales come from the min / max of each batch)')
+            if section.get('per_image', False):
+                raise ValueError('train.fake_quantize: per_image together with range: {type: ema} is not built: the fixed '
+                                 'range has no per-image form (per-image scales come from the min / max of each image)')
             rng = {'momentum': float(m), 'frozen': False}
     return section, bits, rng
 
@@ -89,12 +98,25 @@ def fake_quantize_per_channel_of(config):
     return bool(section.get('per_channel', False)) if section is not None else False
 
 
+def fake_quantize_per_image_of(config):
+    """``train.fake_quantize.per_image`` (a bool, default False; include/hnd_qimage.h): the training-time fake quantiser
+    takes min / max, scale and zero point per image of the batch, which is the quantiser the reference deploys at batch 1.
+    Refused by name: a non-bool, and the key together with ``per_channel`` or ``range: {type: ema}``"""
+    fake_quantize_bits_of(config)
+    section = _fake_quantize_section(config)[0]
+    return bool(section.get('per_image', False)) if section is not None else False
+
+
 def make_config(model='faster_rcnn', method='ghnd', bch=3, batch_size=4, pretrained=True, min_size=None,
                 max_size=None, ckpt_root='./resource/ckpt', fake_quantize_bits=None, fake_quantize_range=None,
-                fake_quantize_per_channel=None):
+                fake_quantize_per_channel=None, fake_quantize_per_image=None):
     """fake_quantize_range: None, or the ``range`` section itself ({'type': 'ema', 'momentum': m} / {'type': 'batch'});
-    fake_quantize_per_channel: None (no key) or the bool of ``per_channel``; both need fake_quantize_bits"""
+    fake_quantize_per_channel / fake_quantize_per_image: None (no key) or the bool of ``per_channel`` / ``per_image``; all
+    three need fake_quantize_bits"""
     config = _make_config(model, method, bch, batch_size, pretrained, min_size, max_size, ckpt_root)
+    if fake_quantize_per_image is not None and fake_quantize_bits is None:
+        raise ValueError('train.fake_quantize must be given num_bits (fake_quantize_bits) for per_image %r'
+                         % (fake_quantize_per_image,))
     if fake_quantize_per_channel is not None and fake_quantize_bits is None:
         raise ValueError('train.fake_quantize must be given num_bits (fake_quantize_bits) for per_channel %r'
                          % (fake_quantize_per_channel,))
@@ -108,6 +130,8 @@ def make_config(model='faster_rcnn', method='ghnd', bch=3, batch_size=4, pretrai
                 if isinstance(fake_quantize_range, dict) else fake_quantize_range
         if fake_quantize_per_channel is not None:
             config['train']['fake_quantize']['per_channel'] = fake_quantize_per_channel
+        if fake_quantize_per_image is not None:
+            config['train']['fake_quantize']['per_image'] = fake_quantize_per_image
         fake_quantize_range_of(config)
     return config
 

@@ -1,21 +1,22 @@
 // The bottleneck quantisers: include/hnd_codec.h (the codec at 1 ... 8 bits and the bit-packed payload), include/hnd_qat.h
-// (the fake quantiser of the training step), include/hnd_qrange.h (the fixed, EMA-calibrated range) and
-// include/hnd_qchannel.h (one scale and zero point per channel), with hnd_quantize_u8 / hnd_dequantize_u8 /
+// (the fake quantiser of the training step), include/hnd_qrange.h (the fixed, EMA-calibrated range), include/hnd_qchannel.h
+// (one scale and zero point per channel) and include/hnd_qimage.h (one per image), with hnd_quantize_u8 / hnd_dequantize_u8 /
 // hnd_roundtrip_f16 of hnd_hip.h.  The formulas and formats are the headers'; the arithmetic is csrc/quant_math.h, whose
 // contract (single correctly rounded fp32 operations, no FMA contraction in this file) makes every path give the same bits
 // for the same scale and zero point.
 //
-// Where a lane's scale and zero point come from is a policy type (PerTensor, PerChannel); the fake quantiser and the packer
-// are one kernel each, built per policy.  quantize / dequantize / unpack_dequantize exist in two lane layouts, because their
-// exports promise different things: the per-tensor exports take any cs >= c with no alignment demand and run one thread per
-// float; the per-channel exports (qc_*) demand cs % 4 == 0 and aligned buffers and run one lane per (pixel, group of 4
-// channels) with the group fastest, so a wave's 16-byte accesses cover consecutive bytes and a lane KEEPS its group: its
-// four scales and zero points are read once.  A pixel wider than the workgroup is walked one workgroup's worth of groups at
-// a time.
+// Where a lane's scale and zero point come from is a policy type (PerTensor, PerChannel, PerImage); the fake quantiser, the
+// packer and the grouped quantise / dequantise / unpack kernels are one kernel each, built per policy.  quantize /
+// dequantize / unpack_dequantize exist in two lane layouts, because their exports promise different things: the per-tensor
+// exports take any cs >= c with no alignment demand and run one thread per float; the per-channel and per-image exports
+// (grouped_*) demand cs % 4 == 0 and aligned buffers and run one lane per (pixel, group of 4 channels) with the group
+// fastest, so a wave's 16-byte accesses cover consecutive bytes and a lane KEEPS its group: its four scales and zero points
+// are read once.  A pixel wider than the workgroup is walked one workgroup's worth of groups at a time.
 #include "common.h"
 #include "hnd_codec.h"
 #include "hnd_qat.h"
 #include "hnd_qchannel.h"
+#include "hnd_qimage.h"
 #include "hnd_qrange.h"
 #include "quant_math.h"
 
@@ -35,6 +36,7 @@ constexpr int kPartBlocks = 512;         // rows of the min / max partial in scr
 constexpr int kMaxC = HND_QCHANNEL_MAX_C;
 constexpr int kFqRows = HND_FAKE_QUANT_TILE_ROWS;
 constexpr int kFqWaves = 4;
+constexpr int kImageBlocks = HND_QIMAGE_PART_BLOCKS;      // rows of the min / max partial in scratch, per image
 
 // ---- the policies.  A policy object is the qparams of one lane's group of 4 channels (k = 0 ... 3 inside the group); its
 // Table (made by stage_table) is the qparams of every channel, for the packer, whose lanes change channel as they go; where
@@ -42,12 +44,18 @@ constexpr int kFqWaves = 4;
 // the fake quantiser's sum of squares: the per-tensor statistics have always been accumulated with a fused multiply-add (the
 // kernel was first built where contraction was on) and the per-channel ones with a rounded product; both are kept, because
 // hnd_bn_finalize's results downstream are compared bit for bit, and they are spelled out so the build flag decides neither.
+// Where the pair follows the PIXEL (PerImage) three more calls say where a lane is: set_image (the grouped kernels, whose
+// grid row is the image when kImageGrid says so), begin_tile / seek_row (the fake quantiser: the tile's first global pixel,
+// then its rows in ascending order) and Table::seek_image (the packer, beside NchwWalk); they are empty everywhere else.
 struct PerTensor {                       // qp[2], qp[3] for every channel
   static constexpr int kPackBound = 1024;                          // the packer's launch bound (the compiler's default)
   float sc, zp;
   __device__ __forceinline__ PerTensor(const float* __restrict__ qp, int, int) : sc(qp[2]), zp(qp[3]) {}
   __device__ __forceinline__ float scale(int) const { return sc; }
   __device__ __forceinline__ float zero(int) const { return zp; }
+  __device__ __forceinline__ void begin_tile(const float* __restrict__, long long, long long) const {}
+  __device__ __forceinline__ void seek_row(const float* __restrict__, int) const {}
+  __device__ __forceinline__ void seek_image(long long) const {}
   static __device__ __forceinline__ float square_sum(float ss, float v) { return __fmaf_rn(v, v, ss); }
   typedef PerTensor Table;                 // one pair for every channel: nothing to stage
   static constexpr bool kTableInLds = false;
@@ -65,13 +73,18 @@ struct PerChannel {                      // qp[ch][4]; channels that are not rea
       zp[k] = real ? qp[(ch0 + k) * 4 + 3] : 0.f;
     }
   }
+  static constexpr bool kImageGrid = false;
   __device__ __forceinline__ float scale(int k) const { return sc[k]; }
   __device__ __forceinline__ float zero(int k) const { return zp[k]; }
+  __device__ __forceinline__ void set_image(const float* __restrict__, long long) const {}
+  __device__ __forceinline__ void begin_tile(const float* __restrict__, long long, long long) const {}
+  __device__ __forceinline__ void seek_row(const float* __restrict__, int) const {}
   static __device__ __forceinline__ float square_sum(float ss, float v) { return __fadd_rn(ss, __fmul_rn(v, v)); }
   struct Table {
     const float *s_scale, *s_zp;
     __device__ __forceinline__ float scale(int ch) const { return s_scale[ch]; }
     __device__ __forceinline__ float zero(int ch) const { return s_zp[ch]; }
+    __device__ __forceinline__ void seek_image(long long) const {}
   };
   static constexpr bool kTableInLds = true;
   // thread ch < c writes channel ch's pair into LDS (at most 512 bytes); the CALLER holds the barrier before any read
@@ -83,6 +96,53 @@ struct PerChannel {                      // qp[ch][4]; channels that are not rea
     }
     return Table{scale_, zp_};
   }
+};
+
+// qp[img][4]: the pair of a lane changes with its pixel's IMAGE, every channel of a pixel shares it.  The [n] pairs are read
+// through the cache, not staged in LDS: a workgroup of the grouped kernels works on ONE image (its grid row; the two floats
+// are the same in every lane, loaded once per workgroup), a fake-quantiser wave's tile of 128 consecutive pixels and a
+// packer lane's 8 consecutive values lie in one image or cross into the next, so each reads one or two of the n pairs --
+// 8 bytes that every lane of the wave asks for at the same address, one cache line -- where staging would have every
+// workgroup load all n pairs and wait at a barrier to use one of them.  The image index is never divided out per float: it
+// is the grid row, or one division per tile and then a walk (seek_row), or NchwWalk's own img (Table::seek_image).
+struct PerImage {
+  static constexpr int kPackBound = kThreads;
+  static constexpr bool kImageGrid = true;
+  float sc, zp;
+  long long img, hw, next;               // the fake quantiser's walk: `next` is the tile row at which image img + 1 begins
+  __device__ __forceinline__ PerImage(const float* __restrict__, int, int) : sc(1.f), zp(0.f), img(0), hw(0), next(0) {}
+  __device__ __forceinline__ float scale(int) const { return sc; }
+  __device__ __forceinline__ float zero(int) const { return zp; }
+  __device__ __forceinline__ void set_image(const float* __restrict__ qp, long long i) {
+    img = i;
+    sc = qp[i * 4 + 2];
+    zp = qp[i * 4 + 3];
+  }
+  __device__ __forceinline__ void begin_tile(const float* __restrict__ qp, long long row0, long long hw_) {
+    hw = hw_;
+    set_image(qp, row0 / hw_);           // the one division of a tile
+    next = (img + 1) * hw_ - row0;
+  }
+  __device__ __forceinline__ void seek_row(const float* __restrict__ qp, int r) {      // r ascending within a tile
+    if (r >= next) {
+      long long i = img;
+      do { ++i; next += hw; } while (r >= next);
+      set_image(qp, i);
+    }
+  }
+  static __device__ __forceinline__ float square_sum(float ss, float v) { return PerTensor::square_sum(ss, v); }
+  struct Table {
+    const float* qp;
+    long long img;
+    float sc, zp;
+    __device__ __forceinline__ float scale(int) const { return sc; }
+    __device__ __forceinline__ float zero(int) const { return zp; }
+    __device__ __forceinline__ void seek_image(long long i) {
+      if (i != img) { img = i; sc = qp[i * 4 + 2]; zp = qp[i * 4 + 3]; }
+    }
+  };
+  static constexpr bool kTableInLds = false;
+  static __device__ __forceinline__ Table stage_table(const float* __restrict__ qp, int) { return Table{qp, -1, 1.f, 0.f}; }
 };
 
 // ---- min / max, per tensor: per-block min / max of the real channels, one partial {lo, hi} per workgroup
@@ -113,8 +173,13 @@ __global__ void minmax_kernel(const float* __restrict__ x, long long npix, int c
 
 // one wave: the batch (lo, hi) from minmax_kernel's partials, then qparams.  With `state` (include/hnd_qrange.h) the batch
 // range is first folded into state = {running_min, running_max, steps, 0} and the qparams are the running range's.
+// Per image (kConstantRule, include/hnd_qimage.h) the grid has one such wave per image: workgroup i reduces the nblocks
+// partials of image i and writes qparams[i], with the rule for a constant image.
+template <bool kConstantRule>
 __global__ void qparams_kernel(const float* __restrict__ part, int nblocks, float momentum, float qmax,
                                float* __restrict__ state, float* __restrict__ qp) {
+  part += (size_t)blockIdx.x * nblocks * 2;
+  qp += (size_t)blockIdx.x * 4;
   float lo = INFINITY, hi = -INFINITY;
   for (int i = threadIdx.x; i < nblocks; i += 64) {
     lo = fminf(lo, part[i * 2]);
@@ -134,7 +199,49 @@ __global__ void qparams_kernel(const float* __restrict__ part, int nblocks, floa
       }
       state[0] = lo; state[1] = hi; state[2] = __fadd_rn(steps, 1.f); state[3] = 0.f;
     }
-    write_qparams<false>(lo, hi, qmax, qp);
+    write_qparams<kConstantRule>(lo, hi, qmax, qp);
+  }
+}
+
+// ---- min / max, per image.  Launch 1 on a grid of (workgroups per image, n): workgroup (b, i) takes its share of image
+// i's pixels, lanes laid out (pixel, group of 4 channels) with the group fastest, one 16-byte load per lane and pixel; only
+// the groups that hold a real channel are read, and of the last group only its real channels count.  The lanes meet by
+// shuffle and then in LDS; one partial {lo, hi} per workgroup, [n][gridDim.x][2] in scratch.  Launch 2 is
+// qparams_kernel<true>.
+__global__ void __launch_bounds__(kThreads) image_minmax_kernel(const float* __restrict__ x, long long hw, int c, int cs,
+                                                                float* __restrict__ part) {
+  __shared__ float smin[4], smax[4];
+  x += (size_t)blockIdx.y * hw * cs;
+  const int gr = (c + 3) >> 2;                                     // groups with a real channel
+  float lo = INFINITY, hi = -INFINITY;
+  for (int gb = 0; gb < gr; gb += kThreads) {
+    const int gc = gr - gb < kThreads ? gr - gb : kThreads;
+    const int slots = kThreads / gc;                               // pixels per pass
+    const int gl = threadIdx.x % gc, slot = threadIdx.x / gc;
+    if (slot >= slots) continue;
+    const int ch0 = (gb + gl) * 4;
+    for (long long p = (long long)blockIdx.x * slots + slot; p < hw; p += (long long)gridDim.x * slots) {
+      const f32x4 v = *(const f32x4*)(x + p * cs + ch0);           // (ch0 + 3 < cs: cs % 4 == 0, cs >= c)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (ch0 + k < c) {
+          lo = fminf(lo, v[k]);
+          hi = fmaxf(hi, v[k]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = fminf(lo, __shfl_xor(lo, o));
+    hi = fmaxf(hi, __shfl_xor(hi, o));
+  }
+  if ((threadIdx.x & 63) == 0) { smin[threadIdx.x >> 6] = lo; smax[threadIdx.x >> 6] = hi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* out = part + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 2;
+    out[0] = fminf(fminf(smin[0], smin[1]), fminf(smin[2], smin[3]));
+    out[1] = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
   }
 }
 
@@ -250,21 +357,26 @@ __global__ void unpack_dequantize_kernel(const uint8_t* __restrict__ payload, co
   }
 }
 
-// ---- the same three, one lane per (pixel, group of 4 channels).  quantise: one 16-byte load and one 4-byte store per lane
-// and pixel; a group without a real channel stores 0 unread
-__global__ void __launch_bounds__(kThreads) qc_quantize_kernel(const float* __restrict__ x, long long npix, int c, int cs,
-                                                               const float* __restrict__ qp, float qmax,
-                                                               uint8_t* __restrict__ q) {
+// ---- the same three, one lane per (pixel, group of 4 channels), built per policy.  The grid's row y takes the npix pixels
+// from pixel y * npix on: the whole tensor in one row per channel, one IMAGE per row (npix = hw) where Params::kImageGrid
+// says so, so that a workgroup's pair is its row's and no lane divides an image index out.  quantise: one 16-byte load and
+// one 4-byte store per lane and pixel; a group without a real channel stores 0 unread
+template <class Params>
+__global__ void __launch_bounds__(kThreads) grouped_quantize_kernel(const float* __restrict__ x, long long npix, int c, int cs,
+                                                                    const float* __restrict__ qp, float qmax,
+                                                                    uint8_t* __restrict__ q) {
   const int groups = cs >> 2;
+  const long long e0 = (long long)blockIdx.y * npix * cs;
   for (int gb = 0; gb < groups; gb += kThreads) {
     const int gc = groups - gb < kThreads ? groups - gb : kThreads;
     const int slots = kThreads / gc;
     const int gl = threadIdx.x % gc, slot = threadIdx.x / gc;
     if (slot >= slots) continue;
     const int ch0 = (gb + gl) * 4;
-    const PerChannel par(qp, ch0, c);
+    Params par(qp, ch0, c);
+    par.set_image(qp, blockIdx.y);
     for (long long p = (long long)blockIdx.x * slots + slot; p < npix; p += (long long)gridDim.x * slots) {
-      const long long e = p * cs + ch0;
+      const long long e = e0 + p * cs + ch0;
       unsigned word = 0;
       if (ch0 < c) {
         const f32x4 v = *(const f32x4*)(x + e);
@@ -278,18 +390,22 @@ __global__ void __launch_bounds__(kThreads) qc_quantize_kernel(const float* __re
 }
 
 // dequantise: one 4-byte load and one 16-byte store per lane and pixel, 0 into the pad channels
-__global__ void __launch_bounds__(kThreads) qc_dequantize_kernel(const uint8_t* __restrict__ q, const float* __restrict__ qp,
-                                                                 float* __restrict__ x, long long npix, int c, int cs) {
+template <class Params>
+__global__ void __launch_bounds__(kThreads) grouped_dequantize_kernel(const uint8_t* __restrict__ q,
+                                                                      const float* __restrict__ qp, float* __restrict__ x,
+                                                                      long long npix, int c, int cs) {
   const int groups = cs >> 2;
+  const long long e0 = (long long)blockIdx.y * npix * cs;
   for (int gb = 0; gb < groups; gb += kThreads) {
     const int gc = groups - gb < kThreads ? groups - gb : kThreads;
     const int slots = kThreads / gc;
     const int gl = threadIdx.x % gc, slot = threadIdx.x / gc;
     if (slot >= slots) continue;
     const int ch0 = (gb + gl) * 4;
-    const PerChannel par(qp, ch0, c);
+    Params par(qp, ch0, c);
+    par.set_image(qp, blockIdx.y);
     for (long long p = (long long)blockIdx.x * slots + slot; p < npix; p += (long long)gridDim.x * slots) {
-      const long long e = p * cs + ch0;
+      const long long e = e0 + p * cs + ch0;
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
       if (ch0 < c) {
         const unsigned word = *(const unsigned*)(q + e);
@@ -303,11 +419,13 @@ __global__ void __launch_bounds__(kThreads) qc_dequantize_kernel(const uint8_t* 
 }
 
 // unpack + dequantise: a lane writes the 16 bytes of its group of a pixel; every real channel reads its value's bits
-__global__ void __launch_bounds__(kThreads) qc_unpack_dequantize_kernel(const uint8_t* __restrict__ payload,
-                                                                        const float* __restrict__ qp, float* __restrict__ x,
-                                                                        long long npix, int c, long long hw, int cs,
-                                                                        int bits) {
+template <class Params>
+__global__ void __launch_bounds__(kThreads) grouped_unpack_dequantize_kernel(const uint8_t* __restrict__ payload,
+                                                                             const float* __restrict__ qp,
+                                                                             float* __restrict__ x, long long npix, int c,
+                                                                             long long hw, int cs, int bits) {
   const int groups = cs >> 2;
+  const long long e0 = (long long)blockIdx.y * npix * cs;
   const unsigned mask = (1u << bits) - 1u;
   for (int gb = 0; gb < groups; gb += kThreads) {
     const int gc = groups - gb < kThreads ? groups - gb : kThreads;
@@ -315,17 +433,18 @@ __global__ void __launch_bounds__(kThreads) qc_unpack_dequantize_kernel(const ui
     const int gl = threadIdx.x % gc, slot = threadIdx.x / gc;
     if (slot >= slots) continue;
     const int ch0 = (gb + gl) * 4;
-    const PerChannel par(qp, ch0, c);
+    Params par(qp, ch0, c);
+    par.set_image(qp, blockIdx.y);
     for (long long p = (long long)blockIdx.x * slots + slot; p < npix; p += (long long)gridDim.x * slots) {
       f32x4 o = {0.f, 0.f, 0.f, 0.f};
       if (ch0 < c) {
-        const long long img = p / hw, pix = p - img * hw;
+        const long long img = Params::kImageGrid ? (long long)blockIdx.y : p / hw, pix = p - (Params::kImageGrid ? 0 : img * hw);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           if (ch0 + k < c)
             o[k] = dequantize_one(payload_code(payload, (img * c + ch0 + k) * hw + pix, bits, mask), par.scale(k), par.zero(k));
       }
-      *(f32x4*)(x + p * cs + ch0) = o;
+      *(f32x4*)(x + e0 + p * cs + ch0) = o;
     }
   }
 }
@@ -334,13 +453,13 @@ __global__ void __launch_bounds__(kThreads) qc_unpack_dequantize_kernel(const ui
 // [i * bits, (i + 1) * bits) of the byte stream, LSB first.  One thread owns a GROUP of 8 consecutive values = `bits` whole
 // bytes starting at byte group * bits, so no two threads share a byte and every store is a plain byte store; the last group
 // holds numel % 8 values when that is not 0 and stores ceil(rem * bits / 8) bytes.  The values of a group are gathered from
-// the NHWC buffer; a group may cross a row, a channel plane or an image, so the channel is tracked per value.
+// the NHWC buffer; a group may cross a row, a channel plane or an image, so the channel and the image are tracked per value.
 template <class Params>
 __global__ void __launch_bounds__(Params::kPackBound) quantize_pack_kernel(const float* __restrict__ x, long long numel, int c,
                                                                             long long hw, int cs, int bits,
                                                                             const float* __restrict__ qp, float qmax,
                                                                             uint8_t* __restrict__ payload) {
-  const typename Params::Table tab = Params::stage_table(qp, c);
+  typename Params::Table tab = Params::stage_table(qp, c);
   if (Params::kTableInLds) __syncthreads();
   const long long groups = (numel + 7) >> 3;
   for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < groups;
@@ -350,6 +469,7 @@ __global__ void __launch_bounds__(Params::kPackBound) quantize_pack_kernel(const
     NchwWalk<long long> at(i0, hw, c);
     unsigned long long word = 0;
     for (int k = 0; k < count; ++k) {
+      tab.seek_image(at.img);
       const float v = quantize_one(x[at.offset(cs)], tab.scale(at.ch), tab.zero(at.ch), qmax);
       word |= (unsigned long long)(unsigned)v << (k * bits);
       at.next();
@@ -370,11 +490,13 @@ __global__ void __launch_bounds__(Params::kPackBound) quantize_pack_kernel(const
 // `mask` (when not null) receives per pixel and group one byte whose bit k says that channel 4 g + k was NOT clipped -- one
 // plain byte store per lane beside its 16-byte store of y, a wave's bytes consecutive like its loads.  Pad channels and the
 // high nibble are 0.
+// include/hnd_qimage.h builds it with PerImage: the tiles run over the global pixel index, `hw` pixels to an image (unused
+// by the other policies), and a tile that straddles two images quantises each row on its own image's pair.
 template <class Params, bool kMask>
 __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const float* x, float* y, long long npix, int c,
                                                                       int cs, const float* __restrict__ qp, float qmax,
                                                                       float* __restrict__ stats, int ntiles,
-                                                                      uint8_t* __restrict__ mask) {
+                                                                      uint8_t* __restrict__ mask, long long hw) {
   __shared__ float red[kFqWaves][64][8];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int groups = cs >> 2;
@@ -387,10 +509,12 @@ __global__ void __launch_bounds__(64 * kFqWaves) fake_quantize_kernel(const floa
       const int slots = 64 / gc;                                  // rows per pass
       const int gl = lane % gc, slot = lane / gc;
       const int ch0 = (gb + gl) * 4;
-      const Params par(qp, ch0, c);
+      Params par(qp, ch0, c);
       float s[4] = {0.f, 0.f, 0.f, 0.f}, ss[4] = {0.f, 0.f, 0.f, 0.f};
       if (slot < slots) {
+        if (rows > 0) par.begin_tile(qp, row0, hw);                // (a wave past the last tile has no image)
         for (int r = slot; r < rows; r += slots) {
+          par.seek_row(qp, r);
           const long long e = (row0 + r) * cs + ch0;
           f32x4 o = {0.f, 0.f, 0.f, 0.f};
           unsigned pass = 0;
@@ -480,7 +604,7 @@ void launch_qparams(const float* x, long long npix, int c, int cs, float qmax, f
   int nb = grid_for(npix * cs);
   if (nb > kPartBlocks) nb = kPartBlocks;
   hipLaunchKernelGGL(minmax_kernel, dim3(nb), dim3(kThreads), 0, s, x, npix, c, cs, scratch);
-  hipLaunchKernelGGL(qparams_kernel, dim3(1), dim3(64), 0, s, scratch, nb, momentum, qmax, state, qparams);
+  hipLaunchKernelGGL(qparams_kernel<false>, dim3(1), dim3(64), 0, s, scratch, nb, momentum, qmax, state, qparams);
 }
 
 void qc_launch_qparams(const float* x, long long npix, int c, int cs, float qmax, float* qparams, float* scratch,
@@ -490,6 +614,27 @@ void qc_launch_qparams(const float* x, long long npix, int c, int cs, float qmax
   const int nb = (int)(b > kPartBlocks ? kPartBlocks : b);
   hipLaunchKernelGGL(qc_minmax_kernel, dim3(nb), dim3(kThreads), 0, s, x, npix, c, cs, scratch);
   hipLaunchKernelGGL(qc_qparams_kernel, dim3(1), dim3(kThreads), 0, s, scratch, nb, c, cs, qmax, qparams);
+}
+
+// per image: workgroups per image for hw pixels when a pass of one workgroup takes `slots` of them, at most `cap`
+inline int image_blocks(long long hw, int slots, int cap) {
+  const long long b = (hw + slots - 1) / slots;
+  return (int)(b > cap ? cap : b);
+}
+
+void image_launch_qparams(const float* x, int n, long long hw, int c, int cs, float qmax, float* qparams, float* scratch,
+                          hipStream_t s) {
+  const int gr = (c + 3) >> 2;
+  const int nb = image_blocks(hw, kThreads / (gr < kThreads ? gr : kThreads), kImageBlocks);
+  hipLaunchKernelGGL(image_minmax_kernel, dim3(nb, n), dim3(kThreads), 0, s, x, hw, c, cs, scratch);
+  hipLaunchKernelGGL(qparams_kernel<true>, dim3(n), dim3(64), 0, s, scratch, nb, 0.f, qmax, (float*)nullptr, qparams);
+}
+
+// the grid of the grouped kernels per image: (workgroups per image, n), about kMaxBlocks workgroups in all
+inline dim3 image_grid(int n, long long hw, int cs) {
+  const int groups = cs >> 2;
+  const int cap = kMaxBlocks / n;
+  return dim3(image_blocks(hw, kThreads / (groups < kThreads ? groups : kThreads), cap < 1 ? 1 : cap), n);
 }
 
 void launch_quantize(const float* x, long long npix, int c, int cs, const float* qparams, float qmax, uint8_t* q,
@@ -507,11 +652,11 @@ void launch_pack(const float* x, int n, int h, int w, int c, int cs, int bits, c
 
 template <class Params, bool kMask>
 void launch_fake_quantize(const float* x, float* y, long long npix, int c, int cs, int bits, const float* qparams,
-                          float* stats, int ntiles, uint8_t* mask, hipStream_t s) {
+                          float* stats, int ntiles, uint8_t* mask, hipStream_t s, long long hw = 0) {
   int nb = (ntiles + kFqWaves - 1) / kFqWaves;
   if (nb > kMaxBlocks) nb = kMaxBlocks;
   hipLaunchKernelGGL((fake_quantize_kernel<Params, kMask>), dim3(nb), dim3(64 * kFqWaves), 0, s, x, y, npix, c, cs, qparams,
-                     qmax_of(bits), stats, ntiles, mask);
+                     qmax_of(bits), stats, ntiles, mask, hw);
 }
 
 // hnd_quantize_bits, and hnd_quantize_u8 as its 8-bit case: the caller has checked its arguments under its own name
@@ -545,6 +690,12 @@ int quantize_bits(const char* who, const float* x, long long npix, int c, int cs
   HND_REQUIRE(cs >= c && cs % 4 == 0, who ": bad pixel stride %d (cs >= c, cs %% 4 == 0)", cs)
 #define REQUIRE_POSITIVE_NPIX(who) HND_REQUIRE(npix > 0, who ": npix must be positive")
 #define REQUIRE_POSITIVE_NHW(who) HND_REQUIRE(n > 0 && h > 0 && w > 0, who ": n, h and w must be positive")
+// per image (reads hw as well; the pack / unpack exports make it from h and w first)
+#define REQUIRE_IMAGES(who)                                                                                   \
+  HND_REQUIRE(n >= 1 && n <= HND_QIMAGE_MAX_N, who ": n %d outside 1 ... %d", n, HND_QIMAGE_MAX_N);            \
+  HND_REQUIRE(hw > 0, who ": hw (h, w) must be positive");                                                    \
+  HND_REQUIRE(c > 0 && cs >= c && cs % 4 == 0, who ": bad pixel (c %d > 0, stride %d >= c, stride %% 4 == 0)", c, cs); \
+  HND_REQUIRE(hw <= LLONG_MAX / cs / n, who ": too many pixels (n * hw * cs must fit an int64)")
 
 extern "C" {
 
@@ -715,7 +866,7 @@ int hnd_qchannel_quantize_bits(const float* x, int64_t npix, int c, int cs, int 
   HND_REQUIRE(aligned(16, x) && aligned(4, q), "hnd_qchannel_quantize_bits: x must be 16-byte aligned and q 4-byte aligned");
   hipStream_t s = hnd::as_stream(stream);
   qc_launch_qparams(x, (long long)npix, c, cs, qmax_of(bits), qparams, scratch, s);
-  hipLaunchKernelGGL(qc_quantize_kernel, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, s, x, (long long)npix, c, cs, qparams,
+  hipLaunchKernelGGL(grouped_quantize_kernel<PerChannel>, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, s, x, (long long)npix, c, cs, qparams,
                      qmax_of(bits), q);
   return hnd::check_launch("hnd_qchannel_quantize_bits");
 }
@@ -725,7 +876,7 @@ int hnd_qchannel_dequantize_u8(const uint8_t* q, const float* qparams, float* x,
   REQUIRE_CHANNELS("hnd_qchannel_dequantize_u8");
   REQUIRE_POSITIVE_NPIX("hnd_qchannel_dequantize_u8");
   HND_REQUIRE(aligned(16, x) && aligned(4, q), "hnd_qchannel_dequantize_u8: x must be 16-byte aligned and q 4-byte aligned");
-  hipLaunchKernelGGL(qc_dequantize_kernel, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, hnd::as_stream(stream), q, qparams,
+  hipLaunchKernelGGL(grouped_dequantize_kernel<PerChannel>, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, hnd::as_stream(stream), q, qparams,
                      x, (long long)npix, c, cs);
   return hnd::check_launch("hnd_qchannel_dequantize_u8");
 }
@@ -751,7 +902,7 @@ int hnd_qchannel_unpack_dequantize_bits(const uint8_t* payload, const float* qpa
   REQUIRE_POSITIVE_NHW("hnd_qchannel_unpack_dequantize_bits");
   HND_REQUIRE(aligned(16, x), "hnd_qchannel_unpack_dequantize_bits: x must be 16-byte aligned");
   const long long hw = (long long)h * w, npix = hw * n;
-  hipLaunchKernelGGL(qc_unpack_dequantize_kernel, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, hnd::as_stream(stream),
+  hipLaunchKernelGGL(grouped_unpack_dequantize_kernel<PerChannel>, dim3(pixel_grid(npix, cs)), dim3(kThreads), 0, hnd::as_stream(stream),
                      payload, qparams, x, npix, c, hw, cs, bits);
   return hnd::check_launch("hnd_qchannel_unpack_dequantize_bits");
 }
@@ -769,6 +920,77 @@ int hnd_qchannel_fake_quantize_bits(const float* x, float* y, int64_t npix, int 
   qc_launch_qparams(x, (long long)npix, c, cs, qmax_of(bits), qparams, scratch, s);
   launch_fake_quantize<PerChannel, false>(x, y, (long long)npix, c, cs, bits, qparams, stats, ntiles, nullptr, s);
   return hnd::check_launch("hnd_qchannel_fake_quantize_bits");
+}
+
+// ---- include/hnd_qimage.h: one (scale, zero point) per image
+int hnd_qimage_abi(void) { return HND_QIMAGE_ABI; }
+
+size_t hnd_qimage_scratch_elems(int n) {
+  if (n < 1 || n > HND_QIMAGE_MAX_N) return 0;
+  return (size_t)n * kImageBlocks * 2;
+}
+
+int hnd_qimage_quantize_bits(const float* x, int n, int64_t hw, int c, int cs, int bits, uint8_t* q, float* qparams,
+                             float* scratch, void* stream) {
+  REQUIRE_POINTERS("hnd_qimage_quantize_bits", x && q && qparams && scratch);
+  REQUIRE_BITS("hnd_qimage_quantize_bits");
+  REQUIRE_IMAGES("hnd_qimage_quantize_bits");
+  HND_REQUIRE(aligned(16, x) && aligned(4, q), "hnd_qimage_quantize_bits: x must be 16-byte aligned and q 4-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  image_launch_qparams(x, n, (long long)hw, c, cs, qmax_of(bits), qparams, scratch, s);
+  hipLaunchKernelGGL(grouped_quantize_kernel<PerImage>, image_grid(n, hw, cs), dim3(kThreads), 0, s, x, (long long)hw, c, cs,
+                     qparams, qmax_of(bits), q);
+  return hnd::check_launch("hnd_qimage_quantize_bits");
+}
+
+int hnd_qimage_dequantize_u8(const uint8_t* q, const float* qparams, float* x, int n, int64_t hw, int c, int cs,
+                             void* stream) {
+  REQUIRE_POINTERS("hnd_qimage_dequantize_u8", q && qparams && x);
+  REQUIRE_IMAGES("hnd_qimage_dequantize_u8");
+  HND_REQUIRE(aligned(16, x) && aligned(4, q), "hnd_qimage_dequantize_u8: x must be 16-byte aligned and q 4-byte aligned");
+  hipLaunchKernelGGL(grouped_dequantize_kernel<PerImage>, image_grid(n, hw, cs), dim3(kThreads), 0, hnd::as_stream(stream), q,
+                     qparams, x, (long long)hw, c, cs);
+  return hnd::check_launch("hnd_qimage_dequantize_u8");
+}
+
+int hnd_qimage_quantize_pack_bits(const float* x, int n, int h, int w, int c, int cs, int bits, uint8_t* payload,
+                                  float* qparams, float* scratch, void* stream) {
+  const long long hw = h > 0 && w > 0 ? (long long)h * w : 0;
+  REQUIRE_POINTERS("hnd_qimage_quantize_pack_bits", x && payload && qparams && scratch);
+  REQUIRE_BITS("hnd_qimage_quantize_pack_bits");
+  REQUIRE_IMAGES("hnd_qimage_quantize_pack_bits");
+  HND_REQUIRE(aligned(16, x), "hnd_qimage_quantize_pack_bits: x must be 16-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  image_launch_qparams(x, n, hw, c, cs, qmax_of(bits), qparams, scratch, s);
+  launch_pack<PerImage>(x, n, h, w, c, cs, bits, qparams, payload, s);
+  return hnd::check_launch("hnd_qimage_quantize_pack_bits");
+}
+
+int hnd_qimage_unpack_dequantize_bits(const uint8_t* payload, const float* qparams, float* x, int n, int h, int w, int c,
+                                      int cs, int bits, void* stream) {
+  const long long hw = h > 0 && w > 0 ? (long long)h * w : 0;
+  REQUIRE_POINTERS("hnd_qimage_unpack_dequantize_bits", payload && qparams && x);
+  REQUIRE_BITS("hnd_qimage_unpack_dequantize_bits");
+  REQUIRE_IMAGES("hnd_qimage_unpack_dequantize_bits");
+  HND_REQUIRE(aligned(16, x), "hnd_qimage_unpack_dequantize_bits: x must be 16-byte aligned");
+  hipLaunchKernelGGL(grouped_unpack_dequantize_kernel<PerImage>, image_grid(n, hw, cs), dim3(kThreads), 0,
+                     hnd::as_stream(stream), payload, qparams, x, hw, c, hw, cs, bits);
+  return hnd::check_launch("hnd_qimage_unpack_dequantize_bits");
+}
+
+int hnd_qimage_fake_quantize_bits(const float* x, float* y, int n, int64_t hw, int c, int cs, int bits, float* qparams,
+                                  float* scratch, float* stats, void* stream) {
+  REQUIRE_POINTERS("hnd_qimage_fake_quantize_bits", x && y && qparams && scratch);
+  REQUIRE_BITS("hnd_qimage_fake_quantize_bits");
+  REQUIRE_IMAGES("hnd_qimage_fake_quantize_bits");
+  const long long npix = (long long)n * hw;
+  const int ntiles = hnd_fake_quantize_tiles(npix);
+  REQUIRE_TILES("hnd_qimage_fake_quantize_bits");
+  HND_REQUIRE(aligned(16, x, y), "hnd_qimage_fake_quantize_bits: x and y must be 16-byte aligned");
+  hipStream_t s = hnd::as_stream(stream);
+  image_launch_qparams(x, n, (long long)hw, c, cs, qmax_of(bits), qparams, scratch, s);
+  launch_fake_quantize<PerImage, false>(x, y, npix, c, cs, bits, qparams, stats, ntiles, nullptr, s, (long long)hw);
+  return hnd::check_launch("hnd_qimage_fake_quantize_bits");
 }
 
 }  // extern "C"

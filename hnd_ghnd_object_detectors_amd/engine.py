@@ -681,7 +681,8 @@ class HeadEngine(object):
     def bwd_out_bits(self):
         return getattr(self, 'out_bits', None)
 
-    def forward(self, x, training, codec=None, fake_quant_bits=None, fake_quant_range=None, fake_quant_per_channel=False):
+    def forward(self, x, training, codec=None, fake_quant_bits=None, fake_quant_range=None, fake_quant_per_channel=False,
+                fake_quant_per_image=False):
         """fake_quant_bits (1 ... 8, training only; include/hnd_qat.h): the bottleneck tensor z = y[encoder_len - 1] is
         quantised and dequantised IN PLACE between its conv and its BatchNorm (decoder.0), whose batch statistics then come
         from the launch that stored the quantised values.  The backward plan is NOT changed, on purpose: the estimator is
@@ -702,16 +703,29 @@ class HeadEngine(object):
         in-place launch is qchannel_fake_quantize_bits -- min / max, scale and zero point per channel of z -- and its
         partial sums feed bn_finalize as above.  The backward plan is the straight-through one, untouched: the ranges come
         from the tensor, so nothing is clipped beyond rounding and there is no mask.  False: the plan key, the launches and
-        every bit are what they were without the keyword."""
+        every bit are what they were without the keyword.
+
+        fake_quant_per_image (with fake_quant_bits, training only, not with fake_quant_range or fake_quant_per_channel;
+        include/hnd_qimage.h): the in-place launch is qimage_fake_quantize_bits -- min / max, scale and zero point per image of
+        z, so an image is quantised as it would be alone -- under a plan key of its own; its partial sums feed bn_finalize as
+        above and the backward plan is the straight-through one, untouched.  False: nothing changes."""
         if not isinstance(fake_quant_per_channel, bool):
             raise ValueError('HeadEngine.forward: fake_quant_per_channel=%r must be a bool' % (fake_quant_per_channel,))
+        if not isinstance(fake_quant_per_image, bool):
+            raise ValueError('HeadEngine.forward: fake_quant_per_image=%r must be a bool' % (fake_quant_per_image,))
         if fake_quant_bits is not None:
             if isinstance(fake_quant_bits, bool) or not isinstance(fake_quant_bits, int) or not 1 <= fake_quant_bits <= 8:
                 raise ValueError('HeadEngine.forward: fake_quant_bits=%r is outside 1 ... 8' % (fake_quant_bits,))
             if not training:
                 fake_quant_bits = None      # (the eval path is the codec's)
         if fake_quant_bits is None:
-            fake_quant_range, fake_quant_per_channel = None, False
+            fake_quant_range, fake_quant_per_channel, fake_quant_per_image = None, False, False
+        if fake_quant_per_image and fake_quant_range is not None:
+            raise ValueError('HeadEngine.forward: fake_quant_per_image together with fake_quant_range is not built (the '
+                             'fixed range has no per-image form)')
+        if fake_quant_per_image and fake_quant_per_channel:
+            raise ValueError('HeadEngine.forward: fake_quant_per_image together with fake_quant_per_channel is not built '
+                             '(the scales are per image or per channel)')
         if fake_quant_per_channel and fake_quant_range is not None:
             raise ValueError('HeadEngine.forward: fake_quant_per_channel together with fake_quant_range is not built (the '
                              'fixed range has no per-channel form)')
@@ -737,9 +751,9 @@ class HeadEngine(object):
         self._out_buf = self.out_provider(self.out_shape(x)) if self.out_provider is not None else None
         key = (x.data_ptr(), tuple(x.shape), training, ptrs, None if self._out_buf is None else self._out_buf.data_ptr(),
                fake_quant_bits) + (() if range_key is None else (range_key,)) + \
-            (('per_channel',) if fake_quant_per_channel else ())
+            (('per_channel',) if fake_quant_per_channel else ()) + (('per_image',) if fake_quant_per_image else ())
         if key != self.plan_key:
-            self._build_forward(x, training, fake_quant_bits, fake_quant_range, fake_quant_per_channel)
+            self._build_forward(x, training, fake_quant_bits, fake_quant_range, fake_quant_per_channel, fake_quant_per_image)
             self.plan_key = key
             self.bwd_key = None
         b = self.bufs
@@ -773,6 +787,9 @@ class HeadEngine(object):
                     if self.fq_per_channel:
                         ops.qchannel_fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch,
                                                         stats=self.stats[i])
+                    elif self.fq_per_image:
+                        ops.qimage_fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch,
+                                                      stats=self.stats[i])
                     elif self.fq_range is None:
                         ops.fake_quantize_bits(self.y[i], hc.cout, fake_quant_bits, qparams, scratch, stats=self.stats[i])
                     else:
@@ -788,7 +805,8 @@ class HeadEngine(object):
                         mask_out=self.out_bits)
         return self.out
 
-    def _build_forward(self, x, training, fake_quant_bits=None, fake_quant_range=None, fake_quant_per_channel=False):
+    def _build_forward(self, x, training, fake_quant_bits=None, fake_quant_range=None, fake_quant_per_channel=False,
+                       fake_quant_per_image=False):
         n, h, w, c = x.shape
         assert c == self.layers[0].cs_in
         b = self.bufs
@@ -832,13 +850,20 @@ class HeadEngine(object):
             self.count.append(m)
             cur, cur_scale, cur_shift, cur_relu = y, sc, sh, hc.relu
             h, w = oh, ow
-        self.fq, self.fq_per_channel = None, False
+        self.fq, self.fq_per_channel, self.fq_per_image = None, False, False
         if training and fake_quant_bits is not None and fake_quant_per_channel:
             # the same launch with a scale and a zero point per channel: qparams [cout, 4] and the wider min / max scratch
             zi = self.encoder_len - 1
             self.fq_per_channel = True
             self.fq = (b.get('fqc_qparams', (self.layers[zi].cout, 4)),
                        b.get('fqc_scratch', (ops.qchannel_scratch_elems(self.layers[zi].cs_out),)))
+            self.ntiles[zi] = ops.fake_quantize_tiles(self.count[zi])
+            self.stats[zi] = b.get('fq_stats', (self.ntiles[zi], 2, self.layers[zi].cs_out))
+        elif training and fake_quant_bits is not None and fake_quant_per_image:
+            # the same launch with a scale and a zero point per image: qparams [n, 4] and n images' worth of min / max scratch
+            zi = self.encoder_len - 1
+            self.fq_per_image = True
+            self.fq = (b.get('fqi_qparams', (n, 4)), b.get('fqi_scratch', (ops.qimage_scratch_elems(n),)))
             self.ntiles[zi] = ops.fake_quantize_tiles(self.count[zi])
             self.stats[zi] = b.get('fq_stats', (self.ntiles[zi], 2, self.layers[zi].cs_out))
         elif training and fake_quant_bits is not None:

@@ -179,6 +179,9 @@ def distill(teacher_model, student_model, train_loader, val_loader, device, dist
     # ... with a scale and a zero point per channel (train.fake_quantize.per_channel; include/hnd_qchannel.h): no state, so
     # nothing for sync_buffers() or the checkpoint; every rank takes the ranges of its own batch
     layer1.train_fake_quant_per_channel = configs.fake_quantize_per_channel_of(config)
+    # ... or per image (train.fake_quantize.per_image; include/hnd_qimage.h): no state either, and nothing is exchanged under
+    # DistributedStudent -- an image is quantised on its own range, so however the global batch is sharded over the ranks
+    layer1.train_fake_quant_per_image = configs.fake_quantize_per_image_of(config)
     # ... on a fixed range (train.fake_quantize.range: {type: ema}): every rank keeps its own qrange_state, like
     # BatchNorm's batch statistics; sync_buffers() carries rank 0's copy everywhere before a validation pass, the
     # checkpoint stores it as host floats under `bottleneck_range` (one synchronisation per saved checkpoint), and a codec

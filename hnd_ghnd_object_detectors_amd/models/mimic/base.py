@@ -50,6 +50,9 @@ class BottleneckBase4Ext(nn.Module):
         # ... with a scale and a zero point per channel (an extension; yaml train.fake_quantize.per_channel; include/
         # hnd_qchannel.h).  Read with train_fake_quant_bits; not together with train_fake_quant_range
         self.train_fake_quant_per_channel = False
+        # ... or per image of the batch (an extension; yaml train.fake_quantize.per_image; include/hnd_qimage.h): the
+        # quantiser the reference deploys at batch 1.  Not together with per_channel or train_fake_quant_range
+        self.train_fake_quant_per_image = False
         # ... on a FIXED range (an extension; yaml train.fake_quantize.range: {type: ema}; include/hnd_qrange.h): see the
         # property train_fake_quant_range.  None = the range of each batch
         self._fq_range = None
@@ -145,6 +148,15 @@ class BottleneckBase4Ext(nn.Module):
         if self.train_fake_quant_per_channel and self._fq_range is not None:
             raise ValueError('train_fake_quant_per_channel together with train_fake_quant_range (train.fake_quantize.range: '
                              '{type: ema}) is not built: the fixed range has no per-channel form')
+        if not isinstance(self.train_fake_quant_per_image, bool):
+            raise ValueError('train_fake_quant_per_image (train.fake_quantize.per_image)=%r must be a bool'
+                             % (self.train_fake_quant_per_image,))
+        if self.train_fake_quant_per_image and self.train_fake_quant_per_channel:
+            raise ValueError('train_fake_quant_per_image together with train_fake_quant_per_channel is not built: the scales '
+                             'are per image or per channel')
+        if self.train_fake_quant_per_image and self._fq_range is not None:
+            raise ValueError('train_fake_quant_per_image together with train_fake_quant_range (train.fake_quantize.range: '
+                             '{type: ema}) is not built: the fixed range has no per-image form')
         if self.encoder._forward_hooks:
             raise NotImplementedError(
                 'fake quantisation (train.fake_quantize) together with a hook / loss term on backbone.body.layer1.encoder '
@@ -172,7 +184,9 @@ class BottleneckBase4Ext(nn.Module):
                           **({} if fq_bits is None or self._fq_range is None
                              else {'fake_quant_range': self._fake_quant_range_arg()}),
                           **({} if fq_bits is None or not self.train_fake_quant_per_channel
-                             else {'fake_quant_per_channel': True}))
+                             else {'fake_quant_per_channel': True}),
+                          **({} if fq_bits is None or not self.train_fake_quant_per_image
+                             else {'fake_quant_per_image': True}))
         body = self.__dict__.get('_body')
         z = None
         if self.encoder._forward_hooks or self.decoder._forward_hooks:

@@ -120,6 +120,19 @@ def split_rcnn_model_per_channel(model, num_bits, packed=False):
     return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)
 
 
+def split_rcnn_model_per_image(model, num_bits, packed=False):
+    """split_rcnn_model whose head quantises with a scale and a zero point PER IMAGE of the batch (include/hnd_qimage.h; min /
+    max of every image's own [c, h, w] slice of the padded batch) and whose tail dequantises with them: an image's codes are
+    those of split_rcnn_model on the same slice alone, whatever else is in the batch.  ``num_bits``: 1 ... 8; ``packed``: the
+    head emits the bit-packed link payload, whose format is split_rcnn_model's; 8 bytes per image cross the link beside it
+    instead of 8 per tensor."""
+    if num_bits is None:
+        raise ValueError('split_rcnn_model_per_image needs a quantization width (1 ... 8)')
+    encoder_transformer = Compose([Quantizer(num_bits=num_bits, packed=packed, per_image=True)])
+    decoder_transformer = Compose([Dequantizer(num_bits=num_bits)])
+    return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)
+
+
 def split_rcnn_model_entropy(model, quantization, static_range=None, code_lengths=None):
     """split_rcnn_model whose head emits the ENTROPY-CODED link payload (structure.transformer.EntropyBottleneck,
     include/hnd_entropy.h) and whose tail decodes and dequantises it in one launch: the detections are those of

@@ -1135,6 +1135,99 @@ def qchannel_fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=No
     return out
 
 
+# include/hnd_qimage.h: one (scale, zero point) per image.  x is the NHWC fp32 buffer [N, H, W, cs] with c real channels;
+# qparams is device float[N][4] = {min, max, scale, zero_point}
+QIMAGE_MAX_N = _lib.QIMAGE_MAX_N
+
+
+def qimage_abi():
+    return int(_L.hnd_qimage_abi())
+
+
+def qimage_scratch_elems(n):
+    """floats of the `scratch` buffer of the quantising per-image calls for n images; 0 for a bad n"""
+    return int(_L.hnd_qimage_scratch_elems(int(n)))
+
+
+def _qi_geometry(who, x, c):
+    """(n, h, w, cs) of the NHWC buffer x [N, H, W, cs] with c real channels"""
+    if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.dtype == torch.float32 and x.is_contiguous()):
+        raise ValueError('%s: needs a contiguous float32 NHWC buffer [N, H, W, cs]' % who)
+    n, h, w, cs = x.shape
+    if isinstance(c, bool) or not isinstance(c, int) or not 0 < c <= cs or cs % 4 or x.numel() == 0:
+        raise ValueError('%s: c=%r real channels in a pixel stride of %d floats (0 < c <= stride, stride %% 4 == 0)'
+                         % (who, c, cs))
+    if n > QIMAGE_MAX_N:
+        raise ValueError('%s: %d images, at most %d per call' % (who, n, QIMAGE_MAX_N))
+    return n, h, w, cs
+
+
+def _qi_scratch(who, scratch, n):
+    if not (isinstance(scratch, torch.Tensor) and scratch.dtype == torch.float32 and scratch.is_contiguous()
+            and scratch.numel() >= qimage_scratch_elems(n)):
+        raise ValueError('%s: scratch must be a contiguous fp32 buffer of qimage_scratch_elems(%d) = %d floats'
+                         % (who, n, qimage_scratch_elems(n)))
+    return scratch
+
+
+def qimage_quantize_bits(x, c, bits, q, qparams, scratch):
+    """quantize_bits with the range of every image its own: one value per byte into q (uint8, x's shape), pad channels 0"""
+    who = 'qimage_quantize_bits'
+    _q_bits(who, bits)
+    n, h, w, cs = _qi_geometry(who, x, c)
+    _q_like(who, 'q', q, x, torch.uint8, True)
+    check(_L.hnd_qimage_quantize_bits(ptr(x), n, h * w, c, cs, bits, ptr(q), ptr(_q_qparams(who, qparams, n)),
+                                      ptr(_qi_scratch(who, scratch, n)), stream_ptr()), 'hnd_qimage_quantize_bits')
+
+
+def qimage_dequantize_u8(q, qparams, x, c):
+    """the inverse: scale[img] * (q - zero_point[img]) into the c real channels of x, 0 into its pad channels"""
+    who = 'qimage_dequantize_u8'
+    n, h, w, cs = _qi_geometry(who, x, c)
+    _q_like(who, 'q', q, x, torch.uint8, True)
+    check(_L.hnd_qimage_dequantize_u8(ptr(q), ptr(_q_qparams(who, qparams, n)), ptr(x), n, h * w, c, cs, stream_ptr()),
+          'hnd_qimage_dequantize_u8')
+    return x
+
+
+def qimage_quantize_pack_bits(x, c, bits, payload, qparams, scratch):
+    """quantize_pack_bits with the range of every image its own: the payload format is that of include/hnd_codec.h"""
+    who = 'qimage_quantize_pack_bits'
+    _q_bits(who, bits)
+    n, h, w, cs = _qi_geometry(who, x, c)
+    _q_payload(who, payload, x, c, bits, 'channel')
+    check(_L.hnd_qimage_quantize_pack_bits(ptr(x), n, h, w, c, cs, bits, ptr(payload), ptr(_q_qparams(who, qparams, n)),
+                                           ptr(_qi_scratch(who, scratch, n)), stream_ptr()),
+          'hnd_qimage_quantize_pack_bits')
+
+
+def qimage_unpack_dequantize_bits(payload, qparams, x, c, bits):
+    """the inverse: scale[img] * (q - zero_point[img]) into the c real channels of x [N, H, W, cs], 0 into its pad channels"""
+    who = 'qimage_unpack_dequantize_bits'
+    _q_bits(who, bits)
+    n, h, w, cs = _qi_geometry(who, x, c)
+    _q_payload(who, payload, x, c, bits, 'channel')
+    check(_L.hnd_qimage_unpack_dequantize_bits(ptr(payload), ptr(_q_qparams(who, qparams, n)), ptr(x), n, h, w, c, cs,
+                                               bits, stream_ptr()), 'hnd_qimage_unpack_dequantize_bits')
+    return x
+
+
+def qimage_fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None):
+    """fake_quantize_bits with the range of every image its own -- the bits of qimage_dequantize_u8(qimage_quantize_bits(x))
+    -- into `out` (default: in place), 0 into the pad channels; `stats` [fake_quantize_tiles(npix), 2, cs] receives the
+    per-tile (sum, sum of squares) of what was stored, tiles over all n * h * w pixels, for bn_finalize.  Returns the
+    destination."""
+    who = 'qimage_fake_quantize_bits'
+    _q_bits(who, bits)
+    n, h, w, cs = _qi_geometry(who, x, c)
+    out = _q_like(who, 'out', x if out is None else out, x, torch.float32, True)
+    _q_stats(who, stats, n * h * w, cs, True)
+    check(_L.hnd_qimage_fake_quantize_bits(ptr(x), ptr(out), n, h * w, c, cs, bits, ptr(_q_qparams(who, qparams, n)),
+                                           ptr(_qi_scratch(who, scratch, n)), ptr(stats), stream_ptr()),
+          'hnd_qimage_fake_quantize_bits')
+    return out
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

@@ -4,7 +4,8 @@ The reference applies them ONLY at evaluation time with ``-transform_bottleneck`
 mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantizer`` run as fused HIP kernels
 (global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
 payload, include/hnd_codec.h, or entropy-coded in chunks, include/hnd_entropy.h; dequantise) on the NHWC bottleneck buffer;
-the 16-bit variants are a half round trip.  ``per_channel=True`` (an extension, include/hnd_qchannel.h) gives every channel
+the 16-bit variants are a half round trip.  ``per_image=True`` (an extension, include/hnd_qimage.h) gives every image of a
+batch a scale and a zero point of its own.  ``per_channel=True`` (an extension, include/hnd_qchannel.h) gives every channel
 of the bottleneck a scale and a zero point of its own, in the plain, the packed and the fake quantiser.
 ``FakeQuantizer`` (an extension) is the pair as one call (include/hnd_qat.h) -- the launch the TRAINING step runs on the
 bottleneck tensor when ``train.fake_quantize`` is set (engine.HeadEngine.forward).
@@ -191,10 +192,13 @@ class JpegCompressor(object):
     """reference :94-114: a 3-channel bottleneck ([3, H, W] or [1, 3, H, W]) is quantised to uint8 (HIP kernel),
     written as a JPEG file and replaced by ``(file path, quantised tensor)``; anything else passes through"""
 
-    def __init__(self, jpeg_quality=95, tmp_dir_path='./tmp/', per_channel=False):
+    def __init__(self, jpeg_quality=95, tmp_dir_path='./tmp/', per_channel=False, per_image=False):
         if _check_per_channel('JpegCompressor', per_channel):
             raise ValueError('JpegCompressor(per_channel=True): the JPEG file carries one scale and zero point; per-channel '
                              'scales are built for Quantizer / FakeQuantizer at 1 ... 8 bits only')
+        if _check_per_image('JpegCompressor', per_image):
+            raise ValueError('JpegCompressor(per_image=True): a JPEG file is one image with one scale and zero point already; '
+                             'per-image scales are built for Quantizer / FakeQuantizer at 1 ... 8 bits only')
         self.jpeg_quality, self.tmp_dir_path = jpeg_quality, tmp_dir_path
         os.makedirs(tmp_dir_path, exist_ok=True)
         self._quantizer = Quantizer(8)
@@ -237,13 +241,14 @@ class QuantizedTensor(object):
     """myutils tensor_util.QuantizedTensor: .tensor (uint8, logical NCHW), .scale, .zero_point.  scale / zero_point
     are 0-dim DEVICE tensors (views of the kernel's qparams) so no host sync is forced; int()/float() work.
     ``per_channel`` (an extension, include/hnd_qchannel.h): qparams is [c, 4], scale / zero_point are its 1-D views
-    qparams[:, 2] / qparams[:, 3], and ``num_bits`` is the width it was quantised at."""
+    qparams[:, 2] / qparams[:, 3], and ``num_bits`` is the width it was quantised at.  ``per_image`` (an extension,
+    include/hnd_qimage.h): the same with one row of qparams per image, [n, 4]."""
 
     def __init__(self, tensor, scale, zero_point, qparams=None, origin=None, channels=None, per_channel=False,
-                 num_bits=None):
+                 num_bits=None, per_image=False):
         self.tensor, self.scale, self.zero_point = tensor, scale, zero_point
         self.qparams, self.origin, self.channels = qparams, origin, channels
-        self.per_channel, self.num_bits = bool(per_channel), num_bits
+        self.per_channel, self.per_image, self.num_bits = bool(per_channel), bool(per_image), num_bits
 
 
 class PackedBottleneck(object):
@@ -252,12 +257,16 @@ class PackedBottleneck(object):
     back to back, ``num_bits`` each, least significant bit first (format: include/hnd_codec.h); ``scale`` /
     ``zero_point`` are 0-dim device views of ``qparams`` as in QuantizedTensor.  An extension: the reference ships the
     one-value-per-byte tensor whatever the width.  ``per_channel`` (include/hnd_qchannel.h): the same payload format beside a
-    ``qparams`` of shape [c, 4]; ``scale`` / ``zero_point`` are its 1-D views qparams[:, 2] / qparams[:, 3]."""
+    ``qparams`` of shape [c, 4]; ``scale`` / ``zero_point`` are its 1-D views qparams[:, 2] / qparams[:, 3].  ``per_image``
+    (include/hnd_qimage.h): the same payload format beside a ``qparams`` of shape [n, 4], one row per image."""
 
-    def __init__(self, payload, shape, num_bits, qparams, origin=None, per_channel=False):
+    def __init__(self, payload, shape, num_bits, qparams, origin=None, per_channel=False, per_image=False):
         self.payload, self.shape, self.num_bits = payload, tuple(int(s) for s in shape), num_bits
-        self.qparams, self.origin, self.per_channel = qparams, origin, bool(per_channel)
-        self.scale, self.zero_point = (qparams[:, 2], qparams[:, 3]) if self.per_channel else (qparams[2], qparams[3])
+        self.qparams, self.origin, self.per_channel, self.per_image = qparams, origin, bool(per_channel), bool(per_image)
+        if self.per_channel and self.per_image:
+            raise ValueError('PackedBottleneck(per_channel=True, per_image=True): the qparams are per channel or per image')
+        rows = self.per_channel or self.per_image
+        self.scale, self.zero_point = (qparams[:, 2], qparams[:, 3]) if rows else (qparams[2], qparams[3])
 
     @property
     def nbytes(self):
@@ -265,8 +274,8 @@ class PackedBottleneck(object):
 
     @property
     def link_bytes(self):
-        """everything that crosses the link: the payload and one (scale, zero point) per tensor or per channel"""
-        return self.nbytes + 8 * (self.shape[1] if self.per_channel else 1)
+        """everything that crosses the link: the payload and one (scale, zero point) per tensor, per channel or per image"""
+        return self.nbytes + 8 * (self.shape[1] if self.per_channel else self.shape[0] if self.per_image else 1)
 
 
 MAX_CODE_LEN = 12          # longest code of include/hnd_entropy.h
@@ -396,6 +405,29 @@ def _check_per_channel_combination(who, num_bits, static_range, entropy=False):
                          'round trip, no scale)' % who)
 
 
+def _check_per_image(who, per_image):
+    """``per_image`` of Quantizer / FakeQuantizer / JpegCompressor: a bool, anything else is refused by name"""
+    if not isinstance(per_image, bool):
+        raise ValueError('%s: per_image=%r must be a bool' % (who, per_image))
+    return per_image
+
+
+def _check_per_image_combination(who, num_bits, static_range, entropy=False, per_channel=False):
+    """per-image scales (include/hnd_qimage.h) exist for the per-batch range at 1 ... 8 bits, plain, packed and fake
+    quantised; every other combination is refused by name"""
+    if per_channel:
+        raise ValueError('%s(per_image=True, per_channel=True): the scales are per image or per channel, the combination is '
+                         'not built' % who)
+    if entropy:
+        raise ValueError('%s(per_image=True, entropy=True): the entropy coder has no per-image form' % who)
+    if static_range is not None:
+        raise ValueError('%s(per_image=True, static_range=%r): a fixed range has no per-image form (per-image scales come '
+                         'from the min / max of each image in front of the call)' % (who, static_range))
+    if num_bits == 16:
+        raise ValueError('%s(num_bits=16, per_image=True): per-image scales need a width of 1 ... 8 bits (16 is a half '
+                         'round trip, no scale)' % who)
+
+
 class _StaticRange(object):
     """``static_range`` of Quantizer / FakeQuantizer (include/hnd_qrange.h): None (min / max of the tensor in front of the
     call, three launches), a pair ``[lo, hi]`` (a fixed range: hnd_qrange_qparams runs once per pair and device, and every
@@ -469,13 +501,14 @@ class _StaticRange(object):
 
 
 class _PerChannelKeyword(type):
-    """``Quantizer(..., per_channel=...)``: the keyword is taken off the call here and handed to ``_init_per_channel`` once
-    ``__init__`` has run, so ``Quantizer.__init__`` keeps the parameter list it has had since the entropy coder (callers and
-    tools that read it by ``inspect.signature`` see no change)"""
+    """``Quantizer(..., per_channel=..., per_image=...)``: the keywords are taken off the call here and handed to
+    ``_init_per_channel`` / ``_init_per_image`` once ``__init__`` has run, so ``Quantizer.__init__`` keeps the parameter list
+    it has had since the entropy coder (callers and tools that read it by ``inspect.signature`` see no change)"""
 
-    def __call__(cls, *args, per_channel=False, **kwargs):
+    def __call__(cls, *args, per_channel=False, per_image=False, **kwargs):
         self = super().__call__(*args, **kwargs)
         self._init_per_channel(per_channel)
+        self._init_per_image(per_image)
         return self
 
 
@@ -488,12 +521,17 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
     host and the encoder's three launches.  ``code_lengths`` (with ``entropy``) fixes the table instead -- all 2^num_bits
     lengths non-zero -- and the call then has neither the histogram nor the read-back.  ``per_channel=True`` (an extension,
     1 ... 8 bits, plain or ``packed``; not with ``entropy`` or ``static_range``): min / max, scale and zero point per channel
-    (include/hnd_qchannel.h); the result carries ``per_channel=True`` and a ``qparams`` of shape [c, 4]."""
+    (include/hnd_qchannel.h); the result carries ``per_channel=True`` and a ``qparams`` of shape [c, 4].  ``per_image=True``
+    (an extension, 1 ... 8 bits, plain or ``packed``; not with ``per_channel``, ``entropy`` or ``static_range``): min / max,
+    scale and zero point per IMAGE of the batch (include/hnd_qimage.h), so image i gets the codes ``Quantizer(num_bits)``
+    gives z[i:i+1] alone; the result carries ``per_image=True`` and a ``qparams`` of shape [n, 4].  The range of an image
+    runs over its whole [c, h, w] slice of the batch tensor, padding included."""
 
     def __init__(self, num_bits=8, packed=False, static_range=None, entropy=False, code_lengths=None):
         _check_bits('Quantizer', num_bits, packed)
         self.num_bits, self.packed, self.entropy = num_bits, bool(packed), bool(entropy)
         self.per_channel = False            # (the keyword: _PerChannelKeyword / _init_per_channel)
+        self.per_image = False              # (the keyword: _PerChannelKeyword / _init_per_image)
         if self.entropy and self.packed:
             raise ValueError('Quantizer(entropy=True, packed=True): the link payload is either entropy-coded or bit-packed')
         if self.entropy and num_bits == 16:
@@ -510,6 +548,11 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
         self.per_channel = _check_per_channel('Quantizer', per_channel)
         if self.per_channel:
             _check_per_channel_combination('Quantizer', self.num_bits, self.static_range, self.entropy)
+
+    def _init_per_image(self, per_image):
+        self.per_image = _check_per_image('Quantizer', per_image)
+        if self.per_image:
+            _check_per_image_combination('Quantizer', self.num_bits, self.static_range, self.entropy, self.per_channel)
 
     def _entropy_code(self, q, c, qparams, shape, origin):
         """q (uint8 NHWC, one value per byte) -> EntropyBottleneck: [histogram, one 1 KB read-back, huffman_lengths] unless
@@ -542,18 +585,24 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
             n, h, w, cs = buf.shape
             qshape = (ops.codec_packed_bytes(n * c * h * w, self.num_bits),) if self.packed else buf.shape
             self._bufs[key] = (torch.empty(qshape, dtype=torch.uint8, device=buf.device),
-                               torch.empty((c, 4) if self.per_channel else (4,), dtype=torch.float32, device=buf.device),
+                               torch.empty((c, 4) if self.per_channel else (n, 4) if self.per_image else (4,),
+                                           dtype=torch.float32, device=buf.device),
                                torch.empty(ops.qchannel_scratch_elems(cs) if self.per_channel else
+                                           ops.qimage_scratch_elems(n) if self.per_image else
                                            ops.minmax_scratch_elems(), dtype=torch.float32, device=buf.device))
         q, qparams, scratch = self._bufs[key]
-        bits, per_channel = self.num_bits, self.per_channel
-        fixed = None if per_channel else self._static_qparams_on(buf.device)
+        bits, per_channel, per_image = self.num_bits, self.per_channel, self.per_image
+        fixed = None if per_channel or per_image else self._static_qparams_on(buf.device)
         # per flavour: the packing call, the one-value-per-byte call (closures: their argument lists differ; one of the two
         # runs) and the qparams the result carries
         if per_channel:                     # a scale and a zero point per channel (include/hnd_qchannel.h)
             qp = qparams
             pack = lambda: ops.qchannel_quantize_pack_bits(buf, c, bits, q, qp, scratch)
             plain = lambda: ops.qchannel_quantize_bits(buf, c, bits, q, qp, scratch)
+        elif per_image:                     # a scale and a zero point per image (include/hnd_qimage.h)
+            qp = qparams
+            pack = lambda: ops.qimage_quantize_pack_bits(buf, c, bits, q, qp, scratch)
+            plain = lambda: ops.qimage_quantize_bits(buf, c, bits, q, qp, scratch)
         elif fixed is not None:             # one launch on the fixed range (include/hnd_qrange.h)
             qp = fixed
             pack = lambda: ops.quantize_pack_range_bits(buf, c, bits, q, qp)
@@ -565,15 +614,16 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
                 ops.quantize_bits(buf, c, bits, q, qp, scratch)
         if self.packed:
             pack()
-            return PackedBottleneck(q, z.shape, bits, qp, origin=buf, per_channel=per_channel), target
+            return PackedBottleneck(q, z.shape, bits, qp, origin=buf, per_channel=per_channel, per_image=per_image), target
         plain()
-        if self.entropy:                    # never per channel: _check_per_channel_combination refuses the pair by name
-            assert not per_channel
+        if self.entropy:                    # never per channel or per image: the combination checks refuse the pair by name
+            assert not per_channel and not per_image
             return self._entropy_code(q, c, qp, z.shape, buf), target
         qt = q[..., :c].permute(0, 3, 1, 2)
-        scale, zero_point = (qp[:, 2], qp[:, 3]) if per_channel else (qp[2], qp[3])
+        rows = per_channel or per_image
+        scale, zero_point = (qp[:, 2], qp[:, 3]) if rows else (qp[2], qp[3])
         return QuantizedTensor(attach(qt, q), scale, zero_point, qp, origin=buf, channels=c, per_channel=per_channel,
-                               num_bits=bits if per_channel else None), target
+                               num_bits=bits if rows else None, per_image=per_image), target
 
 
 class Dequantizer(object):
@@ -581,7 +631,7 @@ class Dequantizer(object):
     scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``; an
     EntropyBottleneck is decoded and dequantised in one launch and must have been coded at ``num_bits``.  A per-channel
     QuantizedTensor / PackedBottleneck (``per_channel=True``, include/hnd_qchannel.h) is recognised by that attribute and
-    must have been quantised at ``num_bits``."""
+    must have been quantised at ``num_bits``; so is a per-image one (``per_image=True``, include/hnd_qimage.h)."""
 
     def __init__(self, num_bits=8):
         _check_bits('Dequantizer', num_bits)
@@ -597,6 +647,8 @@ class Dequantizer(object):
                 torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
             if qz.per_channel:
                 ops.qchannel_unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
+            elif getattr(qz, 'per_image', False):
+                ops.qimage_unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
             else:
                 ops.unpack_dequantize_bits(qz.payload, qz.qparams, out, c, qz.num_bits)
             return attach(out[..., :c].permute(0, 3, 1, 2), out), target
@@ -612,12 +664,17 @@ class Dequantizer(object):
         if isinstance(qz, QuantizedTensor) and qz.per_channel and qz.num_bits != self.num_bits:
             raise ValueError('Dequantizer(num_bits=%d) was handed a per-channel tensor quantised at %d bits'
                              % (self.num_bits, qz.num_bits))
+        if isinstance(qz, QuantizedTensor) and getattr(qz, 'per_image', False) and qz.num_bits != self.num_bits:
+            raise ValueError('Dequantizer(num_bits=%d) was handed a per-image tensor quantised at %d bits'
+                             % (self.num_bits, qz.num_bits))
         if self.num_bits == 16 or not isinstance(qz, QuantizedTensor):
             return qz, target
         q = qz.tensor._hnd
         out = qz.origin if qz.origin is not None else torch.empty(q.shape, dtype=torch.float32, device=q.device)
         if qz.per_channel:
             ops.qchannel_dequantize_u8(q, qz.qparams, out, qz.channels)
+        elif getattr(qz, 'per_image', False):
+            ops.qimage_dequantize_u8(q, qz.qparams, out, qz.channels)
         else:
             ops.dequantize_u8(q, qz.qparams, out, qz.channels)
         z = out[..., :qz.channels].permute(0, 3, 1, 2)
@@ -641,13 +698,18 @@ class FakeQuantizer(_StaticRange):
     such class).  ``qparams`` holds {min, max, scale, zero_point} of the newest call, on the device.  ``static_range``: see
     _StaticRange; the call is then hnd_fake_quantize_range alone.  ``per_channel=True`` (not with ``static_range``): the pair
     ``[Quantizer(num_bits, per_channel=True), Dequantizer(num_bits)]`` as one call (include/hnd_qchannel.h); ``qparams`` is
-    then [c, 4]."""
+    then [c, 4].  ``per_image=True`` (not with ``static_range`` or ``per_channel``): the pair
+    ``[Quantizer(num_bits, per_image=True), Dequantizer(num_bits)]`` as one call (include/hnd_qimage.h); ``qparams`` is then
+    [n, 4]."""
 
-    def __init__(self, num_bits=8, static_range=None, per_channel=False):
+    def __init__(self, num_bits=8, static_range=None, per_channel=False, per_image=False):
         self.num_bits = check_fake_quant_bits('FakeQuantizer', num_bits)
         self.per_channel = _check_per_channel('FakeQuantizer', per_channel)
         if self.per_channel:
             _check_per_channel_combination('FakeQuantizer', num_bits, static_range)
+        self.per_image = _check_per_image('FakeQuantizer', per_image)
+        if self.per_image:
+            _check_per_image_combination('FakeQuantizer', num_bits, static_range, per_channel=self.per_channel)
         self._bufs = {}
         self.qparams = None
         self._init_static_range(static_range)
@@ -664,6 +726,10 @@ class FakeQuantizer(_StaticRange):
             # per flavour: the call, the key of its two buffers, the shape of qparams and the floats of scratch
             if self.per_channel:            # a scale and a zero point per channel (include/hnd_qchannel.h)
                 call, key, qshape, nscratch = ops.qchannel_fake_quantize_bits, (dev, c, cs), (c, 4), ops.qchannel_scratch_elems
+            elif self.per_image:            # a scale and a zero point per image (include/hnd_qimage.h)
+                n = buf.shape[0]
+                call, key, qshape, nscratch = ops.qimage_fake_quantize_bits, (dev, 'n', n), (n, 4), \
+                    lambda cs: ops.qimage_scratch_elems(n)
             else:
                 call, key, qshape, nscratch = ops.fake_quantize_bits, dev, (4,), lambda cs: ops.minmax_scratch_elems()
             if key not in self._bufs:
