@@ -1,7 +1,8 @@
 """ctypes binding of libhnd_hip.so, derived from its C headers: include/hnd_hip.h, hnd_optim.h (the further optimizer
 kinds), hnd_codec.h (the 1 ... 8-bit bottleneck codec) and hnd_qat.h (the fake-quantised bottleneck of the training step),
 each with a version of its own, and -- beside those four -- hnd_qrange.h (the fixed quantisation range of the bottleneck)
-hnd_entropy.h (the entropy-coded link payload), hnd_qchannel.h (per-channel scales) and hnd_qimage.h (per-image scales), with versions of their own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
+hnd_entropy.h (the entropy-coded link payload), hnd_qchannel.h (per-channel scales), hnd_qimage.h (per-image scales) and
+hnd_istream.h (per-image entropy streams), with versions of their own as well.  parse_header() reads the small grammar those headers use; the struct classes, the enum
 dictionaries, the ABI numbers, the symbol tuples and every restype / argtypes below come from what it read, so the headers
 are the only place the contract is written down.
 
@@ -173,6 +174,14 @@ QIMAGE_MAX_N, QIMAGE_PART_BLOCKS = QIMAGE_HEADER.defines['HND_QIMAGE_MAX_N'], QI
 if QIMAGE_HEADER.structs or QIMAGE_HEADER.enums:
     raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % QIMAGE_HEADER_NAME)
 
+# per-image entropy streams with device-built tables: a ninth header, read as hnd_qimage.h is
+ISTREAM_HEADER_NAME = 'hnd_istream.h'
+ISTREAM_HEADER = _read(ISTREAM_HEADER_NAME)
+ISTREAM_ABI, ISTREAM_SYMBOLS = ISTREAM_HEADER.defines['HND_ISTREAM_ABI'], tuple(sorted(ISTREAM_HEADER.functions))
+ISTREAM_MAX_N = ISTREAM_HEADER.defines['HND_ISTREAM_MAX_N']
+if ISTREAM_HEADER.structs or ISTREAM_HEADER.enums:
+    raise HndLibraryError('%s declares a struct or an enum: it may declare functions only' % ISTREAM_HEADER_NAME)
+
 _lib = None
 
 
@@ -191,7 +200,8 @@ def load():
     # smoke() ran in one process).
     import torch  # noqa: F401
     lib = C.CDLL(LIB_PATH)
-    for header in list(HEADERS.values()) + [QRANGE_HEADER, ENTROPY_HEADER, QCHANNEL_HEADER, QIMAGE_HEADER]:
+    for header in list(HEADERS.values()) + [QRANGE_HEADER, ENTROPY_HEADER, QCHANNEL_HEADER, QIMAGE_HEADER,
+                                                  ISTREAM_HEADER]:
         for name, (res, args) in header.functions.items():
             try:
                 fn = getattr(lib, name)
@@ -215,6 +225,8 @@ def load():
         raise HndLibraryError('libhnd_hip.so per-channel codec ABI %d != expected %d' % (lib.hnd_qchannel_abi(), QCHANNEL_ABI))
     if lib.hnd_qimage_abi() != QIMAGE_ABI:
         raise HndLibraryError('libhnd_hip.so per-image codec ABI %d != expected %d' % (lib.hnd_qimage_abi(), QIMAGE_ABI))
+    if lib.hnd_istream_abi() != ISTREAM_ABI:
+        raise HndLibraryError('libhnd_hip.so per-image stream ABI %d != expected %d' % (lib.hnd_istream_abi(), ISTREAM_ABI))
     _lib = lib
     return lib
 

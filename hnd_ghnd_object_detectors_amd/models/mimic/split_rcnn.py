@@ -13,7 +13,7 @@ from torch import nn
 
 from ... import engine as E
 from ...hipnn import ImageList, attach, to_nhwc
-from ...structure.transformer import Compose, Dequantizer, Quantizer
+from ...structure.transformer import Compose, Dequantizer, ImageStreamQuantizer, Quantizer
 
 
 class RcnnHead(nn.Module):
@@ -129,6 +129,19 @@ def split_rcnn_model_per_image(model, num_bits, packed=False):
     if num_bits is None:
         raise ValueError('split_rcnn_model_per_image needs a quantization width (1 ... 8)')
     encoder_transformer = Compose([Quantizer(num_bits=num_bits, packed=packed, per_image=True)])
+    decoder_transformer = Compose([Dequantizer(num_bits=num_bits)])
+    return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)
+
+
+def split_rcnn_model_image_streams(model, num_bits, code_lengths=None):
+    """split_rcnn_model_per_image whose head emits one self-contained ENTROPY-CODED stream per image
+    (structure.transformer.ImageStreamBottleneck, include/hnd_istream.h: per-image scales, a per-image code table built on
+    the device, no host round trip) and whose tail decodes and dequantises all of them in one launch: the detections are
+    those of split_rcnn_model_per_image at the same width, bit for bit.  ``num_bits``: 1 ... 8; ``code_lengths``: a fixed,
+    complete table of 2^num_bits code lengths for every image (no histogram and no table launch in the head) or None."""
+    if num_bits is None:
+        raise ValueError('split_rcnn_model_image_streams needs a quantization width (1 ... 8)')
+    encoder_transformer = Compose([ImageStreamQuantizer(num_bits=num_bits, code_lengths=code_lengths)])
     decoder_transformer = Compose([Dequantizer(num_bits=num_bits)])
     return RcnnHead(model, encoder_transformer), RcnnTail(model, decoder_transformer)
 

@@ -1228,6 +1228,106 @@ def qimage_fake_quantize_bits(x, c, bits, qparams, scratch, out=None, stats=None
     return out
 
 
+# include/hnd_istream.h: one entropy stream, one code table and one (scale, zero point) per image.  q is the one-value-per-
+# byte uint8 NHWC tensor [N, H, W, cs] of qimage_quantize_bits with c real channels; hist is int32 [N, 256], lengths DEVICE
+# uint8 [N, 256], qparams fp32 [N, 4]
+ISTREAM_MAX_N = _lib.ISTREAM_MAX_N
+
+
+def istream_abi():
+    return int(_L.hnd_istream_abi())
+
+
+def istream_chunks_per_image(chw):
+    """chunks of 256 symbols one image of `chw` values makes; 0 for chw <= 0 or chw > 2^30"""
+    return int(_L.hnd_istream_chunks_per_image(int(chw)))
+
+
+def istream_capacity(n, chw):
+    """bytes the payload buffer of n images of `chw` values must have: 384 per chunk; 0 for bad arguments"""
+    return int(_L.hnd_istream_capacity(int(n), int(chw)))
+
+
+def istream_scratch_bytes(n, chw):
+    """bytes of the encoder's scratch buffer; 0 for bad arguments"""
+    return int(_L.hnd_istream_scratch_bytes(int(n), int(chw)))
+
+
+def _istream_geometry(who, t, c, bits, dtype):
+    """(n, h, w, cs, chunks per image) of the NHWC buffer t with c real channels"""
+    _q_bits(who, bits)
+    _q_geometry(who, t, c, 'entropy', dtype)
+    n, h, w, cs = t.shape
+    if istream_scratch_bytes(n, c * h * w) == 0:
+        raise ValueError('%s: %d images of %d values: at most %d images and 2^30 values per call'
+                         % (who, n, c * h * w, ISTREAM_MAX_N))
+    return n, h, w, cs, istream_chunks_per_image(c * h * w)
+
+
+def _istream_rows(who, t, name, n, dtype):
+    """a contiguous [n, 256] table: the histograms (int32) or the code lengths (uint8) of n images"""
+    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == (n, 256)):
+        raise ValueError('%s: %s must be a contiguous %s tensor [%d, 256]' % (who, name, str(dtype).replace('torch.', ''), n))
+    return t
+
+
+def istream_histogram(q, c, bits, hist):
+    """hist (int32 [N, 256], zeroed and filled by the call): row i counts the codes of the c real channels of image i"""
+    who = 'istream_histogram'
+    n, h, w, cs, _ = _istream_geometry(who, q, c, bits, torch.uint8)
+    _istream_rows(who, hist, 'hist', n, torch.int32)
+    check(_L.hnd_istream_histogram(ptr(q), n, h, w, c, cs, bits, ptr(hist), stream_ptr()), 'hnd_istream_histogram')
+    return hist
+
+
+def istream_build_tables(hist, bits, lengths):
+    """lengths (uint8 [N, 256]): row i is transformer.huffman_lengths(hist[i], bits), made on the device in one launch"""
+    who = 'istream_build_tables'
+    _q_bits(who, bits)
+    if not (isinstance(hist, torch.Tensor) and hist.dim() == 2 and 0 < hist.shape[0] <= ISTREAM_MAX_N):
+        raise ValueError('%s: hist must be an int32 tensor [N, 256] of 1 ... %d images' % (who, ISTREAM_MAX_N))
+    n = hist.shape[0]
+    _istream_rows(who, hist, 'hist', n, torch.int32)
+    _istream_rows(who, lengths, 'lengths', n, torch.uint8)
+    check(_L.hnd_istream_build_tables(ptr(hist), n, bits, ptr(lengths), stream_ptr()), 'hnd_istream_build_tables')
+    return lengths
+
+
+def istream_encode(q, c, bits, lengths, payload, offsets, scratch):
+    """offsets (int32 [N * chunks per image + 1]) and the streams (payload, uint8 [istream_capacity]) of the images of q,
+    image i under the canonical code of lengths[i]: three launches, no host synchronisation"""
+    who = 'istream_encode'
+    n, h, w, cs, cpi = _istream_geometry(who, q, c, bits, torch.uint8)
+    _istream_rows(who, lengths, 'lengths', n, torch.uint8)
+    cap = istream_capacity(n, c * h * w)
+    if not (isinstance(payload, torch.Tensor) and payload.dtype == torch.uint8 and payload.is_contiguous()
+            and payload.numel() == cap):
+        raise ValueError('%s: payload must be %d uint8 bytes' % (who, cap))
+    _entropy_words(who, offsets, 'offsets', n * cpi + 1)
+    if not (isinstance(scratch, torch.Tensor) and scratch.is_contiguous()
+            and scratch.numel() * scratch.element_size() >= istream_scratch_bytes(n, c * h * w)):
+        raise ValueError('%s: scratch must hold %d bytes' % (who, istream_scratch_bytes(n, c * h * w)))
+    check(_L.hnd_istream_encode(ptr(q), n, h, w, c, cs, bits, ptr(lengths), ptr(payload), ptr(offsets), ptr(scratch),
+                                stream_ptr()), 'hnd_istream_encode')
+
+
+def istream_decode_dequantize(payload, offsets, lengths, qparams, x, c, bits):
+    """the inverse, fused with the dequantiser: scale[img] * (q - zero_point[img]) into the c real channels of x
+    [N, H, W, cs], 0 into its pad channels, one launch; the bits of qimage_unpack_dequantize_bits on the same codes.
+    `payload` may be the whole capacity or its first offsets[-1] bytes."""
+    who = 'istream_decode_dequantize'
+    n, h, w, cs, cpi = _istream_geometry(who, x, c, bits, torch.float32)
+    _istream_rows(who, lengths, 'lengths', n, torch.uint8)
+    _q_qparams(who, qparams, n)
+    if not (isinstance(payload, torch.Tensor) and payload.dtype == torch.uint8 and payload.is_contiguous()
+            and payload.numel() > 0):
+        raise ValueError('%s: payload must be a non-empty contiguous uint8 buffer' % who)
+    _entropy_words(who, offsets, 'offsets', n * cpi + 1)
+    check(_L.hnd_istream_decode_dequantize(ptr(payload), payload.numel(), ptr(offsets), ptr(lengths), ptr(qparams), ptr(x),
+                                           n, h, w, c, cs, bits, stream_ptr()), 'hnd_istream_decode_dequantize')
+    return x
+
+
 def roundtrip_f16(x):
     check(_L.hnd_roundtrip_f16(ptr(x), x.numel(), stream_ptr()), 'hnd_roundtrip_f16')
 

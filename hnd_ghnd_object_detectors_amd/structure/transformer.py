@@ -5,7 +5,8 @@ mimic_runner.py:90 disables them while distilling).  ``Quantizer`` / ``Dequantiz
 (global min/max -> affine quantise to 1 ... 8 bits, one value per byte as in the reference or bit-packed as the link
 payload, include/hnd_codec.h, or entropy-coded in chunks, include/hnd_entropy.h; dequantise) on the NHWC bottleneck buffer;
 the 16-bit variants are a half round trip.  ``per_image=True`` (an extension, include/hnd_qimage.h) gives every image of a
-batch a scale and a zero point of its own.  ``per_channel=True`` (an extension, include/hnd_qchannel.h) gives every channel
+batch a scale and a zero point of its own; ``ImageStreamQuantizer`` (an extension, include/hnd_istream.h) adds an
+entropy-coded stream and a device-built code table per image.  ``per_channel=True`` (an extension, include/hnd_qchannel.h) gives every channel
 of the bottleneck a scale and a zero point of its own, in the plain, the packed and the fake quantiser.
 ``FakeQuantizer`` (an extension) is the pair as one call (include/hnd_qat.h) -- the launch the TRAINING step runs on the
 bottleneck tensor when ``train.fake_quantize`` is set (engine.HeadEngine.forward).
@@ -375,6 +376,65 @@ class EntropyBottleneck(object):
         return self.nbytes + 4 * self.offsets.numel() + (1 << self.num_bits) + 8
 
 
+class ImageStreamBottleneck(object):
+    """The quantised bottleneck as one self-contained entropy stream PER IMAGE (``ImageStreamQuantizer``; format:
+    include/hnd_istream.h): ``payload`` is a 1-D uint8 device tensor of the streams' CAPACITY of which the first ``nbytes``
+    are the images' streams back to back, ``offsets`` an int32 device tensor of n * chunks_per_image + 1 byte offsets,
+    ``lengths`` a DEVICE uint8 tensor [n, 256] (row i: the code lengths of image i), ``qparams`` [n, 4] as
+    include/hnd_qimage.h writes it; ``scale`` / ``zero_point`` are its [n] views.  ``image(i)`` cuts image i's message out
+    as an ordinary EntropyBottleneck."""
+
+    def __init__(self, payload, offsets, lengths, shape, num_bits, qparams, origin=None):
+        self.payload, self.offsets, self.lengths = payload, offsets, lengths
+        self.shape, self.num_bits = tuple(int(s) for s in shape), num_bits
+        self.qparams, self.scale, self.zero_point, self.origin = qparams, qparams[:, 2], qparams[:, 3], origin
+        self.chunks_per_image = -(-(self.shape[1] * self.shape[2] * self.shape[3]) // 256)
+        self._bounds = None
+
+    def _image_bounds(self):
+        """where every image's stream begins, and the end of the last: offsets[::chunks_per_image], one small device read,
+        cached"""
+        if self._bounds is None:
+            self._bounds = [int(v) & 0xFFFFFFFF for v in self.offsets[::self.chunks_per_image].cpu().tolist()]
+        return self._bounds
+
+    @property
+    def nbytes(self):
+        """bytes of all streams: offsets[n * chunks_per_image]"""
+        return self._image_bounds()[-1]
+
+    @property
+    def image_nbytes(self):
+        """bytes of every image's stream"""
+        b = self._image_bounds()
+        return [hi - lo for lo, hi in zip(b[:-1], b[1:])]
+
+    @property
+    def image_link_bytes(self):
+        """per image, everything of it that crosses the link: its stream, its chunks_per_image + 1 offsets, its table of
+        lengths, its scale and zero point"""
+        return [v + 4 * (self.chunks_per_image + 1) + (1 << self.num_bits) + 8 for v in self.image_nbytes]
+
+    @property
+    def link_bytes(self):
+        return sum(self.image_link_bytes)
+
+    def image(self, i):
+        """image i's link message as an EntropyBottleneck of shape [1, c, h, w] that shares nothing with this object: a copy
+        of its stream in a buffer of its own (so 16-byte aligned wherever the stream began), its offsets rebased to 0, its
+        code lengths as host bytes and a copy of qparams[i].  The per-tensor Dequantizer takes it as it is."""
+        n, c, h, w = self.shape
+        if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < n:
+            raise IndexError('ImageStreamBottleneck.image(%r): the batch holds images 0 ... %d' % (i, n - 1))
+        bounds, cpi = self._image_bounds(), self.chunks_per_image
+        lo, hi = bounds[i], bounds[i + 1]
+        payload = self.payload.new_zeros(max(hi - lo, 1))          # an image whose table is all zero has no bytes
+        payload[:hi - lo] = self.payload[lo:hi]
+        offsets = self.offsets[i * cpi:(i + 1) * cpi + 1] - (lo - (1 << 32) if lo >= 1 << 31 else lo)     # int32 wraps
+        lengths = bytes(self.lengths[i, :1 << self.num_bits].cpu().tolist())
+        return EntropyBottleneck(payload, offsets.contiguous(), lengths, (1, c, h, w), self.num_bits, self.qparams[i].clone())
+
+
 SUPPORTED_BITS = tuple(range(1, 9)) + (16,)
 
 
@@ -626,12 +686,73 @@ class Quantizer(_StaticRange, metaclass=_PerChannelKeyword):
                                num_bits=bits if rows else None, per_image=per_image), target
 
 
+class ImageStreamQuantizer(object):
+    """Per-image scales AND an entropy-coded stream per image (an extension, include/hnd_istream.h; 1 ... 8 bits): image i of a
+    batch gets the codes, the code table, the bytes and the qparams it gets alone, and ``ImageStreamBottleneck.image(i)`` is
+    a message that decodes without its neighbours.  ``Quantizer(entropy=True, per_image=True)`` stays refused: this class is
+    that combination.  The call is ops.qimage_quantize_bits (the launches of ``Quantizer(num_bits, per_image=True)``),
+    ops.istream_histogram, ops.istream_build_tables -- the tables are made on the device, nothing is read back -- and
+    ops.istream_encode; nothing in it synchronises with the host.  ``code_lengths`` fixes one complete table for every image
+    instead (checked as Quantizer's; tiled to [n, 256] once per batch size and device): the call then has neither the
+    histogram nor the table launch.  The buffers of a call are reused by the next call on the same shape."""
+
+    def __init__(self, num_bits=8, code_lengths=None):
+        if isinstance(num_bits, bool) or not isinstance(num_bits, int) or not 1 <= num_bits <= 8:
+            raise ValueError('ImageStreamQuantizer(num_bits=%r): per-image entropy streams need a width of 1 ... 8 bits '
+                             '(16 is a half round trip, no codes)' % (num_bits,))
+        self.num_bits = num_bits
+        self.code_lengths = None if code_lengths is None else \
+            check_code_lengths('ImageStreamQuantizer', code_lengths, num_bits, complete=True)
+        self._bufs, self._tables = {}, {}
+
+    def _buffers(self, buf, c):
+        """per (shape, c, device): q, qparams, the quantiser's scratch, hist, lengths, payload, offsets, the encoder's scratch"""
+        key = (tuple(buf.shape), c, buf.device)
+        if key not in self._bufs:
+            n, h, w, _ = buf.shape
+            chw, dev = c * h * w, buf.device
+            words = ops.istream_scratch_bytes(n, chw) // 4
+            if not words:
+                raise ValueError('ImageStreamQuantizer: %d images of %d values: at most %d images and 2^30 values per call'
+                                 % (n, chw, ops.ISTREAM_MAX_N))
+            self._bufs[key] = (torch.empty(buf.shape, dtype=torch.uint8, device=dev),
+                               torch.empty((n, 4), dtype=torch.float32, device=dev),
+                               torch.empty(ops.qimage_scratch_elems(n), dtype=torch.float32, device=dev),
+                               torch.empty((n, 256), dtype=torch.int32, device=dev),
+                               torch.empty((n, 256), dtype=torch.uint8, device=dev),
+                               torch.empty(ops.istream_capacity(n, chw), dtype=torch.uint8, device=dev),
+                               torch.empty(words + 1, dtype=torch.int32, device=dev),
+                               torch.empty(words, dtype=torch.int32, device=dev))
+        return self._bufs[key]
+
+    def _fixed_table(self, n, device):
+        if (n, device) not in self._tables:
+            row = torch.tensor(list(self.code_lengths) + [0] * (256 - len(self.code_lengths)), dtype=torch.uint8)
+            self._tables[(n, device)] = row.repeat(n, 1).to(device)
+        return self._tables[(n, device)]
+
+    def __call__(self, z, target):
+        buf = to_nhwc(z)                    # [N, H, W, cs] fp32 bottleneck (pad channels are 0)
+        c, bits = z.shape[1], self.num_bits
+        q, qparams, qscratch, hist, lengths, payload, offsets, scratch = self._buffers(buf, c)
+        ops.qimage_quantize_bits(buf, c, bits, q, qparams, qscratch)
+        if self.code_lengths is None:
+            ops.istream_histogram(q, c, bits, hist)
+            ops.istream_build_tables(hist, bits, lengths)
+        else:
+            lengths = self._fixed_table(buf.shape[0], buf.device)
+        ops.istream_encode(q, c, bits, lengths, payload, offsets, scratch)
+        return ImageStreamBottleneck(payload, offsets, lengths, z.shape, bits, qparams, origin=buf), target
+
+
 class Dequantizer(object):
     """reference :143-153.  A QuantizedTensor of any width goes through the one dequantise kernel (the width lives in its
     scale); a PackedBottleneck is unpacked and dequantised in one launch and must have been packed at ``num_bits``; an
     EntropyBottleneck is decoded and dequantised in one launch and must have been coded at ``num_bits``.  A per-channel
     QuantizedTensor / PackedBottleneck (``per_channel=True``, include/hnd_qchannel.h) is recognised by that attribute and
-    must have been quantised at ``num_bits``; so is a per-image one (``per_image=True``, include/hnd_qimage.h)."""
+    must have been quantised at ``num_bits``; so is a per-image one (``per_image=True``, include/hnd_qimage.h).  An
+    ImageStreamBottleneck (include/hnd_istream.h) is decoded and dequantised in one launch, every image under its own table
+    and qparams, and must have been coded at ``num_bits``."""
 
     def __init__(self, num_bits=8):
         _check_bits('Dequantizer', num_bits)
@@ -660,6 +781,15 @@ class Dequantizer(object):
             out = qz.origin if qz.origin is not None else \
                 torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
             ops.entropy_decode_dequantize(qz.payload, qz.offsets, qz.lengths, qz.qparams, out, c, qz.num_bits)
+            return attach(out[..., :c].permute(0, 3, 1, 2), out), target
+        if isinstance(qz, ImageStreamBottleneck):
+            if qz.num_bits != self.num_bits:
+                raise ValueError('Dequantizer(num_bits=%d) was handed per-image streams entropy-coded at %d bits'
+                                 % (self.num_bits, qz.num_bits))
+            n, c, h, w = qz.shape
+            out = qz.origin if qz.origin is not None else \
+                torch.empty((n, h, w, ops.chan_pad_of(c)), dtype=torch.float32, device=qz.payload.device)
+            ops.istream_decode_dequantize(qz.payload, qz.offsets, qz.lengths, qz.qparams, out, c, qz.num_bits)
             return attach(out[..., :c].permute(0, 3, 1, 2), out), target
         if isinstance(qz, QuantizedTensor) and qz.per_channel and qz.num_bits != self.num_bits:
             raise ValueError('Dequantizer(num_bits=%d) was handed a per-channel tensor quantised at %d bits'
@@ -752,7 +882,8 @@ def resolve_trained_ranges(transformer, info):
 
 
 TRANSFORMER_CLASS_DICT = {'jpeg_compressor': JpegCompressor, 'jpeg_decompressor': JpegDecompressor,
-                          'quantizer': Quantizer, 'dequantizer': Dequantizer, 'fake_quantizer': FakeQuantizer}
+                          'quantizer': Quantizer, 'dequantizer': Dequantizer, 'fake_quantizer': FakeQuantizer,
+                          'image_stream_quantizer': ImageStreamQuantizer}
 
 
 def get_bottleneck_transformer(transformer_config):
