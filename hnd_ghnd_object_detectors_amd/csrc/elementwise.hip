@@ -1064,6 +1064,10 @@ __global__ void subsample2_kernel(const float* __restrict__ x, float* __restrict
 // ops/feature_pyramid_network.py): fine pixel (Y, X) reads coarse pixel (floor(Y h / H), floor(X w / W)), so coarse pixel
 // (y, x) receives the sum over its preimage rows [ceil(y H / h), ceil((y + 1) H / h)) x columns likewise -- a fixed order
 // (row-major), no atomics.  accumulate: added to what g_coarse holds.
+// Domain: the rule here is the exact integer floor(Y h / H); torch's is floorf(Y * (float)h / (float)H) in fp32.  The two
+// give the same index for every fine pixel when H < 1500 and h is ceil(H / 2), floor(H / 2) or H -- every pair of
+// neighbouring FPN levels -- and NOT for arbitrary pairs, e.g. (h, H) = (820, 1122)
+// (tests/test_elementwise_cases_cpu.py sweeps the domain and pins that pair).
 __global__ void upsample_nearest_bwd_kernel(const float* __restrict__ g_fine, float* __restrict__ g_coarse, int n, int H,
                                             int W, int h, int w, int c, int accumulate) {
   const int c4n = c >> 2;

@@ -700,7 +700,9 @@ def subsample2(x, y):
 
 def upsample_nearest_bwd(g_fine, g_coarse, accumulate):
     """backward of F.interpolate(coarse, size=fine.shape, mode='nearest'): g_coarse (+)= the sums of g_fine over the fine
-    pixels that read each coarse one (NHWC, same channels)"""
+    pixels that read each coarse one (NHWC, same channels).  Domain: the kernel's source index is the exact integer
+    floor(Y h / H), torch's is floorf(Y * (float)h / (float)H); they agree for every H < 1500 with h in
+    {ceil(H / 2), floor(H / 2), H} (neighbouring FPN levels), not for arbitrary pairs such as (h, H) = (820, 1122)."""
     n, H, W, c = g_fine.shape
     nc, h, w, cc = g_coarse.shape
     assert (n, c) == (nc, cc) and g_fine.is_contiguous() and g_coarse.is_contiguous()
