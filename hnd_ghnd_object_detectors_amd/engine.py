@@ -239,7 +239,7 @@ def wino_tile_for(tile, n, h, w):
     same alone and inside a batch (tests: batch-16 maps == batch-1 maps bit for bit)."""
     if tile != 4 or not WINOGRAD6:
         return tile
-    return 6 if ((h + 5) // 6) * ((w + 5) // 6) >= WINOGRAD6_MIN_TILES else 4
+    return 6 if ops.wino_tiles(h, w, 6) >= WINOGRAD6_MIN_TILES else 4
 
 
 WINOGRAD2_6 = True          # (settled in round 3; was HND_WINOGRAD2_6)
@@ -251,7 +251,16 @@ def wino2_tile_for(oh, ow):
     the activation; fp32 error 4.1e-6 vs 1.7e-6 relative L2.  Map size only, never the batch (see wino_tile_for)."""
     if not WINOGRAD2_6:
         return 4
-    return 6 if ((oh + 5) // 6) * ((ow + 5) // 6) >= WINOGRAD6_MIN_TILES else 4
+    return 6 if ops.wino_tiles(oh, ow, 6) >= WINOGRAD6_MIN_TILES else 4
+
+
+def _wino_scratch(engine, launch, n, oh, ow, cin, cout, tile):
+    """V / M scratch of the Winograd launches of one engine (they run one after another on one stream): the largest
+    launch.scratch_elems (ops.WinoConv / ops.Wino2Conv) asked of this engine so far."""
+    nv, nm = launch.scratch_elems(n, oh, ow, cin, cout, tile)
+    cur = getattr(engine, '_wino_need', (0, 0))
+    engine._wino_need = (max(nv, cur[0]), max(nm, cur[1]))
+    return engine.bufs.get('wino_v', (engine._wino_need[0],)), engine.bufs.get('wino_m', (engine._wino_need[1],))
 
 
 # =========================================================================================== transform
@@ -494,7 +503,7 @@ class FrozenLayerEngine(object):
             bits_step = a2b is not None
             if b.wino_tile:             # stride-1 3x3, >= 256 channels: Winograd F(2x2,3x3)
                 tile = wino_tile_for(b.wino_tile, n, h, w)
-                v, m = self._wino_scratch(n, h, w, b.planes, b.planes, tile)
+                v, m = _wino_scratch(self, ops.WinoConv, n, h, w, b.planes, b.planes, tile)
                 in_transform = a2b is not None and tile in (4, 6)
                 self.fwd += ops.WinoConv(a1, b.w2.wino(False, tile), a2, v, m, epi_scale=a2f[0], epi_shift=a2f[1],
                                          relu=True, mask_out=a2b if in_transform else None).launches(tagp + '.conv2')
@@ -528,11 +537,6 @@ class FrozenLayerEngine(object):
         self.out = cur
         self.flops_fwd = flops
 
-    def _wino_scratch(self, n, h, w, cin, cout, tile=None):
-        """V / M scratch of the Winograd launches of this engine (they run one after another on one stream)."""
-        nv, nm = ops.WinoConv.scratch_elems(n, h, w, cin, cout, tile or WINOGRAD)
-        self._wino_need = (max(nv, getattr(self, '_wino_need', (0, 0))[0]), max(nm, getattr(self, '_wino_need', (0, 0))[1]))
-        return self.bufs.get('wino_v', (self._wino_need[0],)), self.bufs.get('wino_m', (self._wino_need[1],))
 
     # ---- backward: self.g_out holds the gradient w.r.t. this layer's output, already masked by out > 0
     def block_out(self, i):
@@ -594,7 +598,7 @@ class FrozenLayerEngine(object):
             # conv2 (3x3, stride s): g_a1 = [a1>0] * dgrad(g_a2 * s2)
             if b.wino_tile:
                 tile = wino_tile_for(b.wino_tile, n, h, w)
-                v, m = self._wino_scratch(n, h, w, b.planes, b.planes, tile)
+                v, m = _wino_scratch(self, ops.WinoConv, n, h, w, b.planes, b.planes, tile)
                 self.bwd += ops.WinoConv(g_a2, b.w2.wino(True, tile), g_a1, v, m, pro_scale=s2,
                                          mask=a1).launches(tagp + '.conv2.dgrad')
             else:
@@ -825,7 +829,7 @@ class HeadEngine(object):
             sc, sh = b.get('scale%d' % i, (hc.cs_out,)), b.get('shift%d' % i, (hc.cs_out,))
             mu, rs = b.get('mean%d' % i, (hc.cs_out,)), b.get('rstd%d' % i, (hc.cs_out,))
             if hc.wino_f:
-                v, mm = self._wino_scratch(n, oh, ow, hc.cs_in, hc.cs_out, t2)
+                v, mm = _wino_scratch(self, ops.Wino2Conv, n, oh, ow, hc.cs_in, hc.cs_out, t2)
                 if training:        # the transformed input is kept: the weight gradient reuses it
                     v = b.get('wino_keep_v%d' % i,
                               (ops.Wino2Conv.scratch_elems(n, oh, ow, hc.cs_in, hc.cs_out, t2)[0],))
@@ -888,20 +892,10 @@ class HeadEngine(object):
             if (training and MASK_BITS and self.layers[-1].relu and self.layers[-1].cs_out % 4 == 0) else None
         self.flops_fwd = flops
 
-    def _wino_scratch(self, n, oh, ow, cin, cout, tile=4):
-        nv, nm = ops.Wino2Conv.scratch_elems(n, oh, ow, cin, cout, tile)
-        cur = getattr(self, '_wino_need', (0, 0))
-        self._wino_need = (max(nv, cur[0]), max(nm, cur[1]))
-        return self.bufs.get('wino_v', (self._wino_need[0],)), self.bufs.get('wino_m', (self._wino_need[1],))
-
     def _wino_slab_elems(self, fw, hc):
-        """split-K workspace of the grouped Winograd wgrad launch (sized for the largest layer that uses it)"""
-        n, h, w, c, oh, ow = fw.geom
-        d = ops.WgradDesc()
-        tiles = n * ((oh + fw.tile - 1) // fw.tile) * ((ow + fw.tile - 1) // fw.tile)
-        d.n, d.h, d.w_, d.cin, d.cin_real, d.oh, d.ow, d.cout, d.ldy = 1, 1, tiles, c, hc.cin, 1, tiles, hc.cout, hc.cout
-        d.kh, d.kw, d.stride, d.pad, d.groups = 1, 1, 1, 0, fw.ww.ncomp
-        need = (ops.wgrad_workspace_of(d) + 3) // 4
+        """split-K workspace of the grouped Winograd wgrad launch (sized for the largest layer that uses it; not for
+        the swapped descriptor: ops.Wino2Wgrad allocates its own where this one is too small)"""
+        need = (ops.wgrad_workspace_of(ops.Wino2Wgrad.grouped_desc(fw, hc.cout)) + 3) // 4
         self._wino_slab_need = max(need, getattr(self, '_wino_slab_need', 0))
         return self._wino_slab_need
 
@@ -945,7 +939,7 @@ class HeadEngine(object):
                 tag = 'layer1.%s.conv%d' % (part, i)
                 if hc.wino_f:                    # same arithmetic as the unsplit model
                     t2 = wino2_tile_for(oh, ow)
-                    v, mm = self._wino_scratch(n, oh, ow, hc.cs_in, hc.cs_out, t2)
+                    v, mm = _wino_scratch(self, ops.Wino2Conv, n, oh, ow, hc.cs_in, hc.cs_out, t2)
                     plan['convs'] += ops.Wino2Conv(cur, hc.wc.wino2(False, t2), y, v, mm, hc.pad, pro_scale=pro[0],
                                                    pro_shift=pro[1], pro_relu=pro[2]).launches(tag)
                 else:
@@ -1094,11 +1088,11 @@ class HeadEngine(object):
             if dw is not None and i in self.wino_fwd and hc.cs_out == hc.cout and hc.cs_in == hc.cin:
                 # Winograd-domain weight gradient: forward V x transformed dy, 25 grouped split-K reductions
                 fw = self.wino_fwd[i]
-                _, zbuf = self._wino_scratch(fw.geom[0], fw.geom[4], fw.geom[5], hc.cs_in, hc.cs_out, fw.tile)
+                _, zbuf = _wino_scratch(self, ops.Wino2Conv, fw.geom[0], fw.geom[4], fw.geom[5], hc.cs_in, hc.cs_out, fw.tile)
                 if self.bwd_side:       # Z must outlive the data gradient's M (which the shared scratch aliases)
                     zbuf = b.get('wino_z%d' % i, (ops.Wino2Conv.scratch_elems(fw.geom[0], fw.geom[4], fw.geom[5], hc.cs_in,
                                                                              hc.cs_out, fw.tile)[1],))
-                sbuf = b.get('wino_s%d' % i, (fw.ww.ncomp * hc.cout * hc.cin,))
+                sbuf = b.get('wino_s%d' % i, (fw.ncomp * hc.cout * hc.cin,))
                 wg_obj = ops.Wino2Wgrad(fw, gbuf[i], dw, zbuf, sbuf, b.get('wino_slabs', (self._wino_slab_elems(fw, hc),)))
                 st['wgrad'] = wg_obj.launches('layer1.conv%d.wgrad' % i)
                 flops += 2 * npix * hc.cout * 4 * hc.cin
@@ -1109,10 +1103,10 @@ class HeadEngine(object):
                 vw = b.get('wino_vw%d' % i, (ops.Wino2InputTransform.scratch_elems(n_, oh_, ow_, hc.cs_in, 6),))
                 own = ops.Wino2InputTransform(src, vw, hc.pad, hc.cout, 6, pro_scale=pro[0], pro_shift=pro[1],
                                               pro_relu=pro[2])
-                _, zbuf = self._wino_scratch(n_, oh_, ow_, hc.cs_in, hc.cs_out, 6)
+                _, zbuf = _wino_scratch(self, ops.Wino2Conv, n_, oh_, ow_, hc.cs_in, hc.cs_out, 6)
                 if self.bwd_side:
                     zbuf = b.get('wino_z%d' % i, (ops.Wino2Conv.scratch_elems(n_, oh_, ow_, hc.cs_in, hc.cs_out, 6)[1],))
-                sbuf = b.get('wino_s%d' % i, (own.ww.ncomp * hc.cout * hc.cin,))
+                sbuf = b.get('wino_s%d' % i, (own.ncomp * hc.cout * hc.cin,))
                 wg_obj = ops.Wino2Wgrad(own, gbuf[i], dw, zbuf, sbuf, b.get('wino_slabs', (self._wino_slab_elems(own, hc),)))
                 wg = wg_obj.launches('layer1.conv%d.wgrad' % i)
                 st['wgrad'] = [wg[0], own.step('layer1.conv%d.wgrad' % i)] + wg[1:]      # dy transform first (see `fused`)
@@ -1126,7 +1120,7 @@ class HeadEngine(object):
             if tgt is not None and hc.wino_d:
                 nd, hd, wd, _ = tgt.shape
                 t2 = wino2_tile_for(hd, wd)
-                v, mm = self._wino_scratch(nd, hd, wd, hc.cs_out, hc.cs_in, t2)
+                v, mm = _wino_scratch(self, ops.Wino2Conv, nd, hd, wd, hc.cs_out, hc.cs_in, t2)
                 bwd_stats = None
                 prev = self.layers[i - 1] if i > 0 else None
                 if (FOLD_BNBWD_REDUCE and prev is not None and t2 == 6 and prev.cs_out == prev.cout

@@ -94,9 +94,8 @@ def bx3_recommended(rows_per_image, kdim, cout):
     return bool(_L.hnd_bf16x3_recommended(int(rows_per_image), int(kdim), int(cout)))
 
 
-# The two image builders take a packed fp32 buffer and (re)build its image into `out`, or into a new tensor.  An image no
-# longer depends on the emulation mode: `force` is accepted for callers written when it did, and changes nothing.
-def bx3_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=None):
+# The two image builders take a packed fp32 buffer and (re)build its image into `out`, or into a new tensor.
+def bx3_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None):
     """the bf16x3 image (hnd_pack_bf16x3: the B-resident emulation kernel, csrc/conv_bx3.hip)"""
     if out is None:
         out = torch.empty(int(_L.hnd_pack_bf16x3_elems(rows_pad, kdim, groups)), dtype=torch.int16, device=buf.device)
@@ -105,7 +104,7 @@ def bx3_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=Non
     return out
 
 
-def bxs_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None, force=None):
+def bxs_image(buf, rows_pad, kdim, groups=1, group_stride=0, out=None):
     """the STREAM image (hnd_pack_bf16x3s: the B-streamed emulation kernel, csrc/conv_bxs.hip)"""
     if out is None:
         out = torch.empty(int(_L.hnd_pack_bf16x3s_elems(rows_pad, kdim, groups)), dtype=torch.int16, device=buf.device)
@@ -1339,6 +1338,15 @@ def wino_tiles_pad(n, h, w, tile=2):
     return int(_L.hnd_wino_tiles_pad(n, h, w, tile))
 
 
+def wino_tiles(oh, ow, tile):
+    """tile x tile output tiles that cover the oh x ow outputs of ONE image (the last of a row / column may be ragged)"""
+    return ((oh + tile - 1) // tile) * ((ow + tile - 1) // tile)
+
+
+def _stream(stream):
+    return stream if stream is not None else stream_ptr()
+
+
 class _WinogradWeights(PackedWeight):
     """One k x k conv weight in the Winograd domain: a grouped operand of ncomp = (tile+k-1)^2 GEMM matrices
     [rows_pad][depth], one per component; dgrad: of the transposed conv.  The subclasses name k, the tiles and the
@@ -1368,83 +1376,102 @@ class WinoWeights(_WinogradWeights):
         _WinogradWeights.__init__(self, weight, dgrad, tile)
 
 
-def _component_gemms(v, ww, m, cout, tiles_pad, n, oh, ow):
-    """the ww.ncomp component GEMMs V -> M of a Winograd launch with oh x ow outputs per image, as ONE grouped igemm
-    launch (tiles_pad rows per component)"""
-    tiles = ((oh + ww.tile - 1) // ww.tile) * ((ow + ww.tile - 1) // ww.tile)        # per image
-    gemm = conv_desc(v, ww, m, kh=1, kw=1, oh=1, ow=ww.ncomp * tiles_pad, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0, cout=cout,
-                     rows_per_image=ww.ncomp * tiles, w_group_rows=tiles_pad)
-    gemm.flops = 2 * ww.ncomp * n * tiles * ww.rows * ww.depth                   # multiplies actually executed
-    gemm.alg_flops = 2 * n * oh * ow * ww.rows * ww.K ** 2 * ww.depth            # the direct convolution it computes
-    return gemm
+class _WinogradLaunch(object):
+    """What the Winograd launches of one stride-1 K x K correlation with padding `pad` share.  The input half: x [N,H,W,C]
+    -> V = B^T d B in `v`, BN(+ReLU) prologue on load.  With a weight operand `ww` the rest as well: the ncomp =
+    (tile+K-1)^2 component GEMMs V -> M as ONE grouped igemm launch (tiles_pad rows per component, `m`) and the output
+    transform M -> y [N,OH,OW,ldc].  v / m are caller-provided scratch (see scratch_elems).  A subclass names K, ROUND (the
+    rounding of cout), the two transforms (INPUT, OUTPUT: plan labels, 'hnd_' + INPUT the entry point), _tiles_pad,
+    _input_args and, where it has an output, _run_output and _output_bytes."""
 
-
-class WinoConv(object):
-    """One stride-1 pad-1 3x3 convolution (or its data gradient) as input transform -> (tile+2)^2 GEMMs in one igemm
-    launch -> output transform.  x [N,H,W,C] -> y [N,H,W,ldc]; v / m are caller-provided scratch (see scratch_elems)."""
-
-    def __init__(self, x, ww, y, v, m, pro_scale=None, pro_shift=None, pro_relu=False, epi_scale=None, epi_shift=None,
-                 res1=None, mask=None, relu=False, mask_out=None):
-        """mask_out: uint8 nibbles of the STORED output (mask_nibbles_like(y)), written by the output transform (tile 4 / 6)"""
+    def __init__(self, x, v, tile, pad, pro_scale, pro_shift, pro_relu, ww=None, y=None, m=None):
         n, h, w, c = _nhwc(x)
-        assert tuple(y.shape[:3]) == (n, h, w) and c == ww.depth
-        self.x, self.y, self.ww = x, y, ww
-        self.geom = (n, h, w, c)
-        tile, nc = ww.tile, ww.ncomp
-        self.tile = tile
-        self.tiles_pad = wino_tiles_pad(n, h, w, tile)
-        self.cout = round_up(ww.rows, 4)
-        assert self.cout <= y.shape[3]
-        need_v, need_m = nc * self.tiles_pad * c, nc * self.tiles_pad * self.cout
-        assert v.numel() >= need_v and m.numel() >= need_m
+        oh, ow = h + 2 * pad - self.K + 1, w + 2 * pad - self.K + 1
+        self.x, self.y, self.ww, self.pad, self.tile = x, y, ww, pad, tile
+        self.geom = (n, h, w, c, oh, ow)
+        self.ncomp, self.dgrad = (tile + self.K - 1) ** 2, ww is not None and bool(ww.dgrad)
+        self.tiles_pad, self.tiles = self._tiles_pad(n, oh, ow, tile), n * wino_tiles(oh, ow, tile)
+        rows = self.ncomp * self.tiles_pad
+        assert v.numel() >= rows * c
         if pro_scale is not None and pro_shift is None:
             pro_shift = _zeros(c, x.device)
         self.pro = (pro_scale, pro_shift, int(pro_relu))
-        self.epi = (epi_scale, epi_shift, res1, mask, int(relu))
-        self.mask_out = mask_out
-        assert mask_out is None or (tile in (4, 6) and self.cout == y.shape[3] and mask_out.dtype == torch.uint8
-                                    and tuple(mask_out.shape) == tuple(y.shape[:3]) + (y.shape[3] // 4,))
-        for t in (res1, mask):
-            assert t is None or tuple(t.shape) == tuple(y.shape)
-        self.v = v[:need_v].view(1, 1, nc * self.tiles_pad, c)
-        self.m = m[:need_m].view(1, 1, nc * self.tiles_pad, self.cout)
-        self.gemm = _component_gemms(self.v, ww, self.m, self.cout, self.tiles_pad, n, h, w)
+        self.v = v[:rows * c].view(1, 1, rows, c)
+        self.input_bytes = 4 * (n * h * w * c + self.ncomp * self.tiles * c)           # read x once, write V
+        if ww is None:
+            return
+        assert tuple(y.shape[:3]) == (n, oh, ow) and c == ww.depth
+        self.cout = round_up(ww.rows, self.ROUND)
+        assert self.cout <= y.shape[3] and m.numel() >= rows * self.cout
+        self.m = m[:rows * self.cout].view(1, 1, rows, self.cout)
+        self.gemm = conv_desc(self.v, ww, self.m, kh=1, kw=1, oh=1, ow=rows, sh=1, dh=1, bh=0, sw=1, dw=1, bw=0,
+                              cout=self.cout, rows_per_image=self.ncomp * wino_tiles(oh, ow, tile),
+                              w_group_rows=self.tiles_pad)
+        self.gemm.flops = 2 * self.ncomp * self.tiles * ww.rows * ww.depth             # multiplies actually executed
+        self.gemm.alg_flops = 2 * n * oh * ow * ww.rows * self.K ** 2 * ww.depth       # the direct convolution it computes
         self.flops, self.variant = self.gemm.flops, self.gemm.variant
 
-    @staticmethod
-    def scratch_elems(n, h, w, cin, cout, tile=2):
-        tp, nc = wino_tiles_pad(n, h, w, tile), (tile + 2) ** 2
-        return nc * tp * cin, nc * tp * round_up(cout, 4)
+    @classmethod
+    def _scratch_elems(cls, n, oh, ow, cin, cout, tile):
+        rows = (tile + cls.K - 1) ** 2 * cls._tiles_pad(n, oh, ow, tile)
+        return rows * cin, rows * round_up(cout, cls.ROUND)
 
     def _run_input(self, stream=None):
-        n, h, w, c = self.geom
-        check(_L.hnd_wino_input(ptr(self.x), ptr(self.v), n, h, w, c, ptr(self.pro[0]), ptr(self.pro[1]), self.pro[2],
-                                self.tile, stream if stream is not None else stream_ptr()), 'hnd_wino_input')
+        name = 'hnd_' + self.INPUT
+        check(getattr(_L, name)(*self._input_args(), _stream(stream)), name)
 
-    def _run_output(self, stream=None):
-        n, h, w, c = self.geom
-        es, eb, r1, mk, relu = self.epi
-        check(_L.hnd_wino_output(ptr(self.m), ptr(self.y), n, h, w, self.cout, self.y.shape[3], ptr(es), ptr(eb),
-                                 ptr(r1), ptr(mk), relu, self.tile, ptr(self.mask_out),
-                                 stream if stream is not None else stream_ptr()), 'hnd_wino_output')
+    def step(self, tag):
+        """the input transform as an engine plan entry"""
+        return (_Step(self._run_input, self.INPUT, self.input_bytes), tag + '.wino_in')
 
     def launches(self, tag):
         """[(launch, tag)] for an engine plan: the two transforms carry no flops (not event-timed by bench.py), the
         GEMM launch is an ordinary igemm launch with the multiplies it really executes."""
-        n, h, w, c = self.geom
-        nc, tiles = self.ww.ncomp, n * ((h + self.tile - 1) // self.tile) * ((w + self.tile - 1) // self.tile)
-        extra = sum(1 for t in (self.epi[2], self.epi[3]) if t is not None)
-        b_in = 4 * (n * h * w * c + nc * tiles * c)                                 # read x once, write V
-        b_out = 4 * (nc * tiles * self.cout + (1 + extra) * n * h * w * self.cout)  # read M (+ res / mask), write y
-        if self.mask_out is not None:
-            b_out += n * h * w * self.cout // 4
-        return [(_Step(self._run_input, 'wino_input', b_in), tag + '.wino_in'), (self.gemm, tag),
-                (_Step(self._run_output, 'wino_output', b_out), tag + '.wino_out')]
+        return [self.step(tag), (self.gemm, tag),
+                (_Step(self._run_output, self.OUTPUT, self._output_bytes()), tag + '.wino_out')]
 
     def run(self, stream=None):
         self._run_input(stream)
         self.gemm.run(stream)
         self._run_output(stream)
+
+
+class WinoConv(_WinogradLaunch):
+    """One stride-1 pad-1 3x3 convolution (or its data gradient) as input transform -> (tile+2)^2 GEMMs in one igemm
+    launch -> output transform.  x [N,H,W,C] -> y [N,H,W,ldc]."""
+    K, ROUND, INPUT, OUTPUT = 3, 4, 'wino_input', 'wino_output'
+    _tiles_pad = staticmethod(wino_tiles_pad)
+
+    def __init__(self, x, ww, y, v, m, pro_scale=None, pro_shift=None, pro_relu=False, epi_scale=None, epi_shift=None,
+                 res1=None, mask=None, relu=False, mask_out=None):
+        """mask_out: uint8 nibbles of the STORED output (mask_nibbles_like(y)), written by the output transform (tile 4 / 6)"""
+        _WinogradLaunch.__init__(self, x, v, ww.tile, 1, pro_scale, pro_shift, pro_relu, ww, y, m)
+        self.geom = self.geom[:4]                                                   # (oh, ow) == (h, w)
+        self.epi = (epi_scale, epi_shift, res1, mask, int(relu))
+        self.mask_out = mask_out
+        assert mask_out is None or (self.tile in (4, 6) and self.cout == y.shape[3] and mask_out.dtype == torch.uint8
+                                    and tuple(mask_out.shape) == tuple(y.shape[:3]) + (y.shape[3] // 4,))
+        for t in (res1, mask):
+            assert t is None or tuple(t.shape) == tuple(y.shape)
+
+    @classmethod
+    def scratch_elems(cls, n, h, w, cin, cout, tile=2):
+        return cls._scratch_elems(n, h, w, cin, cout, tile)
+
+    def _input_args(self):
+        return (ptr(self.x), ptr(self.v)) + self.geom + (ptr(self.pro[0]), ptr(self.pro[1]), self.pro[2], self.tile)
+
+    def _run_output(self, stream=None):
+        n, h, w, c = self.geom
+        es, eb, r1, mk, relu = self.epi
+        check(_L.hnd_wino_output(ptr(self.m), ptr(self.y), n, h, w, self.cout, self.y.shape[3], ptr(es), ptr(eb),
+                                 ptr(r1), ptr(mk), relu, self.tile, ptr(self.mask_out), _stream(stream)), 'hnd_wino_output')
+
+    def _output_bytes(self):
+        n, h, w, c = self.geom
+        extra = sum(1 for t in (self.epi[2], self.epi[3]) if t is not None)
+        b_out = 4 * (self.ncomp * self.tiles * self.cout + (1 + extra) * n * h * w * self.cout)  # read M (+ res / mask), write y
+        return b_out + n * h * w * self.cout // 4 if self.mask_out is not None else b_out
 
 
 class Wino2Weights(_WinogradWeights):
@@ -1455,7 +1482,20 @@ class Wino2Weights(_WinogradWeights):
         _WinogradWeights.__init__(self, weight, dgrad, tile)
 
 
-class Wino2Conv(object):
+class _Wino2Launch(_WinogradLaunch):
+    """the F(tile x tile, 2x2) launches (tile 4 or 6, padding 0 or 1): geom = (n, h, w, c, oh, ow)"""
+    K, ROUND, INPUT, OUTPUT = 2, 2, 'wino2_input', 'wino2_output'
+
+    @staticmethod
+    def _tiles_pad(n, oh, ow, tile):
+        return int(_L.hnd_wino2_tiles_pad(n, oh, ow, tile))
+
+    def _input_args(self):
+        return (ptr(self.x), ptr(self.v)) + self.geom[:4] + (self.pad, ptr(self.pro[0]), ptr(self.pro[1]), self.pro[2],
+                                                             self.tile)
+
+
+class Wino2Conv(_Wino2Launch):
     """One 2x2 correlation with padding `pad` in {0, 1} (a head conv, or -- with Wino2Weights(dgrad=True) and padding
     1 - pad_of_the_conv -- its data gradient): x [N,H,W,C] -> y [N,H+2pad-1,W+2pad-1,ldc].  Optional BN(+ReLU)
     prologue on load; optional per-block BN statistics of the stored output (stats: [stats_blocks][2][cout])."""
@@ -1465,20 +1505,9 @@ class Wino2Conv(object):
         """bwd_stats = (x_raw, scale, shift, mean, rstd, relu, partials): this launch is the DATA gradient that produces
         the gradient w.r.t. the output of a train-mode BatchNorm(+ReLU) over x_raw; its output transform then also makes
         the BatchNorm-backward partial sums (hnd_wino26_output_bnbwd_stats; F(6x6,2x2), plain epilogue only)."""
-        n, h, w, c = _nhwc(x)
-        oh, ow = h + 2 * pad - 1, w + 2 * pad - 1
-        assert tuple(y.shape[:3]) == (n, oh, ow) and c == ww.depth and pad in (0, 1)
-        self.x, self.y, self.ww, self.pad = x, y, ww, pad
-        self.geom = (n, h, w, c, oh, ow)
-        self.tile, nc = ww.tile, ww.ncomp
-        self.tiles_pad = int(_L.hnd_wino2_tiles_pad(n, oh, ow, self.tile))
-        self.cout = round_up(ww.rows, 2)
-        assert self.cout <= y.shape[3]
-        need_v, need_m = nc * self.tiles_pad * c, nc * self.tiles_pad * self.cout
-        assert v.numel() >= need_v and m.numel() >= need_m
-        if pro_scale is not None and pro_shift is None:
-            pro_shift = _zeros(c, x.device)
-        self.pro = (pro_scale, pro_shift, int(pro_relu))
+        assert pad in (0, 1)
+        _Wino2Launch.__init__(self, x, v, ww.tile, pad, pro_scale, pro_shift, pro_relu, ww, y, m)
+        n, h, w, c, oh, ow = self.geom
         self.epi = (epi_scale, epi_shift, int(relu))
         self.stats = stats
         if stats is not None:
@@ -1488,25 +1517,14 @@ class Wino2Conv(object):
             assert self.tile == 6 and stats is None and epi_scale is None and epi_shift is None and not relu
             assert 512 % self.cout == 0 and tuple(bwd_stats[0].shape) == tuple(y.shape) and y.shape[3] == self.cout
             assert bwd_stats[6].numel() >= self.stats_blocks(n, oh, ow, self.cout, 6) * 2 * self.cout
-        self.v = v[:need_v].view(1, 1, nc * self.tiles_pad, c)
-        self.m = m[:need_m].view(1, 1, nc * self.tiles_pad, self.cout)
-        self.gemm = _component_gemms(self.v, ww, self.m, self.cout, self.tiles_pad, n, oh, ow)
-        self.flops, self.variant = self.gemm.flops, self.gemm.variant
 
-    @staticmethod
-    def scratch_elems(n, oh, ow, cin, cout, tile=4):
-        tp, nc = int(_L.hnd_wino2_tiles_pad(n, oh, ow, tile)), (tile + 1) ** 2
-        return nc * tp * cin, nc * tp * round_up(cout, 2)
+    @classmethod
+    def scratch_elems(cls, n, oh, ow, cin, cout, tile=4):
+        return cls._scratch_elems(n, oh, ow, cin, cout, tile)
 
     @staticmethod
     def stats_blocks(n, oh, ow, cout, tile=4):
         return int(_L.hnd_wino2_stats_blocks(n, oh, ow, cout, tile))
-
-    def _run_input(self, stream=None):
-        n, h, w, c, oh, ow = self.geom
-        check(_L.hnd_wino2_input(ptr(self.x), ptr(self.v), n, h, w, c, self.pad, ptr(self.pro[0]), ptr(self.pro[1]),
-                                 self.pro[2], self.tile, stream if stream is not None else stream_ptr()),
-              'hnd_wino2_input')
 
     def _run_output(self, stream=None):
         n, h, w, c, oh, ow = self.geom
@@ -1514,64 +1532,30 @@ class Wino2Conv(object):
             xr, sc, sh, mu, rs, relu, part = self.bwd_stats
             check(_L.hnd_wino26_output_bnbwd_stats(ptr(self.m), ptr(self.y), n, oh, ow, self.cout, self.y.shape[3],
                                                    ptr(xr), ptr(sc), ptr(sh), ptr(mu), ptr(rs), int(relu), ptr(part),
-                                                   stream if stream is not None else stream_ptr()),
-                  'hnd_wino26_output_bnbwd_stats')
+                                                   _stream(stream)), 'hnd_wino26_output_bnbwd_stats')
             return
         check(_L.hnd_wino2_output(ptr(self.m), ptr(self.y), n, oh, ow, self.cout, self.y.shape[3], ptr(self.epi[0]),
-                                  ptr(self.epi[1]), self.epi[2], ptr(self.stats), self.tile,
-                                  stream if stream is not None else stream_ptr()), 'hnd_wino2_output')
+                                  ptr(self.epi[1]), self.epi[2], ptr(self.stats), self.tile, _stream(stream)),
+              'hnd_wino2_output')
 
-    def launches(self, tag):
+    def _output_bytes(self):
         n, h, w, c, oh, ow = self.geom
-        nc = self.ww.ncomp
-        tiles = n * ((oh + self.tile - 1) // self.tile) * ((ow + self.tile - 1) // self.tile)
-        b_in = 4 * (n * h * w * c + nc * tiles * c)
-        b_out = 4 * (nc * tiles * self.cout + (2 if self.bwd_stats is not None else 1) * n * oh * ow * self.cout)
-        return [(_Step(self._run_input, 'wino2_input', b_in), tag + '.wino_in'), (self.gemm, tag),
-                (_Step(self._run_output, 'wino2_output', b_out), tag + '.wino_out')]
-
-    def run(self, stream=None):
-        self._run_input(stream)
-        self.gemm.run(stream)
-        self._run_output(stream)
+        return 4 * (self.ncomp * self.tiles * self.cout + (2 if self.bwd_stats is not None else 1) * n * oh * ow * self.cout)
 
 
-class Wino2InputTransform(object):
-    """V = B^T d B of a 2x2 conv's input alone (no GEMM, no output): what Wino2Wgrad needs from the forward pass of a conv
-    whose FORWARD is not on the Winograd path (the head's 64 -> 256 conv: its component GEMMs would be 64 deep and
-    HBM-bound, but its weight gradient in the Winograd domain executes 2.9x fewer multiplies than the direct one).  Has the
-    attributes of Wino2Conv that Wino2Wgrad reads."""
+class Wino2InputTransform(_Wino2Launch):
+    """V = B^T d B of a 2x2 conv's input alone (no weights, no GEMM, no output: _run_input and step only): what Wino2Wgrad
+    needs from the forward pass of a conv whose FORWARD is not on the Winograd path (the head's 64 -> 256 conv: its component
+    GEMMs would be 64 deep and HBM-bound, but its weight gradient in the Winograd domain executes 2.9x fewer multiplies than
+    the direct one)."""
 
     def __init__(self, x, v, pad, cout, tile=6, pro_scale=None, pro_shift=None, pro_relu=False):
-        from types import SimpleNamespace
-        n, h, w, c = _nhwc(x)
-        oh, ow = h + 2 * pad - 1, w + 2 * pad - 1
-        assert pad in (0, 1) and tile in (4, 6) and c % 32 == 0
-        self.x, self.pad, self.tile = x, pad, tile
-        self.geom = (n, h, w, c, oh, ow)
-        self.tiles_pad = int(_L.hnd_wino2_tiles_pad(n, oh, ow, tile))
-        self.ww = SimpleNamespace(ncomp=(tile + 1) ** 2, dgrad=False, tile=tile)
-        need = self.ww.ncomp * self.tiles_pad * c
-        assert v.numel() >= need
-        if pro_scale is not None and pro_shift is None:
-            pro_shift = _zeros(c, x.device)
-        self.pro = (pro_scale, pro_shift, int(pro_relu))
-        self.v = v[:need].view(1, 1, self.ww.ncomp * self.tiles_pad, c)
+        assert pad in (0, 1) and tile in (4, 6) and x.shape[3] % 32 == 0
+        _Wino2Launch.__init__(self, x, v, tile, pad, pro_scale, pro_shift, pro_relu)
 
-    @staticmethod
-    def scratch_elems(n, oh, ow, cin, tile=6):
-        return (tile + 1) ** 2 * int(_L.hnd_wino2_tiles_pad(n, oh, ow, tile)) * cin
-
-    def _run_input(self, stream=None):
-        n, h, w, c, oh, ow = self.geom
-        check(_L.hnd_wino2_input(ptr(self.x), ptr(self.v), n, h, w, c, self.pad, ptr(self.pro[0]), ptr(self.pro[1]),
-                                 self.pro[2], self.tile, stream if stream is not None else stream_ptr()),
-              'hnd_wino2_input')
-
-    def step(self, tag):
-        n, h, w, c, oh, ow = self.geom
-        tiles = n * ((oh + self.tile - 1) // self.tile) * ((ow + self.tile - 1) // self.tile)
-        return (_Step(self._run_input, 'wino2_input', 4 * (n * h * w * c + self.ww.ncomp * tiles * c)), tag + '.wino_in')
+    @classmethod
+    def scratch_elems(cls, n, oh, ow, cin, tile=6):
+        return cls._scratch_elems(n, oh, ow, cin, 0, tile)[0]
 
 
 class Wino2Wgrad(object):
@@ -1580,60 +1564,62 @@ class Wino2Wgrad(object):
     wgrad launch and inverse-transforms into dw [cout, cin, 2, 2]."""
 
     def __init__(self, fwd, dy, dw, z, s, slabs=None):
-        assert isinstance(fwd, (Wino2Conv, Wino2InputTransform)) and not fwd.ww.dgrad
+        assert isinstance(fwd, _Wino2Launch) and not fwd.dgrad
         n, h, w, c, oh, ow = fwd.geom
         cout, cin = dw.shape[0], dw.shape[1]
         assert tuple(dw.shape) == (cout, cin, 2, 2) and dw.is_contiguous() and cin == c and cout % 2 == 0
         assert tuple(dy.shape[:3]) == (n, oh, ow) and dy.shape[3] >= cout
-        tp, tile, nc = fwd.tiles_pad, fwd.tile, fwd.ww.ncomp
-        self.tile, self.ncomp = tile, nc
-        tiles = n * ((oh + tile - 1) // tile) * ((ow + tile - 1) // tile)
-        assert z.numel() >= nc * tp * cout and s.numel() >= nc * cout * cin
+        self.tile, self.ncomp, self.tiles = fwd.tile, fwd.ncomp, n * wino_tiles(oh, ow, fwd.tile)
+        nc = self.ncomp
+        assert z.numel() >= nc * fwd.tiles_pad * cout and s.numel() >= nc * cout * cin
         self.fwd, self.dy, self.dw, self.z, self.s = fwd, dy, dw, z, s
         self.geom = (n, oh, ow, cout, dy.shape[3], cin)
-        def grouped(swap):
-            """descriptor of the nc grouped reductions; swap: operands exchanged -> s comes out [comp][cin][cout]"""
-            d = WgradDesc()
-            d.x, d.dy, d.dw = (ptr(z), ptr(fwd.v), ptr(s)) if swap else (ptr(fwd.v), ptr(z), ptr(s))
-            kc, kr = (cout, c) if swap else (c, cout)          # columns ("cin" of the descriptor), rows ("cout")
-            d.n, d.h, d.w_, d.cin, d.cin_real = 1, 1, tiles, kc, kc
-            d.oh, d.ow, d.cout, d.ldy = 1, tiles, kr, kr
-            d.kh, d.kw, d.stride, d.pad, d.splitk = 1, 1, 1, 0, 0
-            d.groups = nc
-            d.x_group_stride, d.dy_group_stride, d.dw_group_stride = tp * kc, tp * kr, cout * cin
-            return d
         # A conv with 64 OUTPUT channels (encoder.5: 256 -> 64) is 64 rows x 256 columns, which only the LDS-staged kernel
         # takes (0.50 of the matrix peak); with the operands swapped it is the 64-column x 256-row shape of the ring
         # kernel (round 5).  The output transform then reads s transposed.
-        d = grouped(False)
+        d = self.grouped_desc(fwd, cout, False, z, s)
         self.swapped = False
-        if (cin == c and int(_L.hnd_conv2d_wgrad_variant(C.byref(d))) != 3
-                and int(_L.hnd_conv2d_wgrad_variant(C.byref(grouped(True)))) == 3
+        if (int(_L.hnd_conv2d_wgrad_variant(C.byref(d))) != 3
+                and int(_L.hnd_conv2d_wgrad_variant(C.byref(self.grouped_desc(fwd, cout, True, z, s)))) == 3
                 and os.environ.get('HND_WGRAD_SWAP', '1') != '0'):
-            d, self.swapped = grouped(True), True
+            d, self.swapped = self.grouped_desc(fwd, cout, True, z, s), True
         need = _L.hnd_conv2d_wgrad_workspace(C.byref(d))
         if slabs is None or slabs.numel() * 4 < need:
             slabs = torch.empty((need + 3) // 4, dtype=torch.float32, device=dy.device)
         d.slabs = ptr(slabs)
-        self.gemm = WgradLaunch(d, (fwd.v, z, s, slabs), 2 * nc * tiles * cout * cin)
+        self.gemm = WgradLaunch(d, (fwd.v, z, s, slabs), 2 * nc * self.tiles * cout * cin)
         self.gemm.alg_flops = 2 * n * oh * ow * cout * 4 * cin
         self.flops, self.variant = self.gemm.flops, self.gemm.variant
 
+    @staticmethod
+    def grouped_desc(fwd, cout, swap=False, z=None, s=None):
+        """descriptor of the fwd.ncomp grouped split-K reductions V x Z -> s of a conv with cout output channels; swap: operands
+        exchanged -> s comes out [comp][cin][cout].  Without z / s: its geometry alone, to size the workspace."""
+        n, h, w, c, oh, ow = fwd.geom
+        tiles, tp = n * wino_tiles(oh, ow, fwd.tile), fwd.tiles_pad
+        d = WgradDesc()
+        d.x, d.dy, d.dw = (ptr(z), ptr(fwd.v), ptr(s)) if swap else (ptr(fwd.v), ptr(z), ptr(s))
+        kc, kr = (cout, c) if swap else (c, cout)          # columns ("cin" of the descriptor), rows ("cout")
+        d.n, d.h, d.w_, d.cin, d.cin_real = 1, 1, tiles, kc, kc
+        d.oh, d.ow, d.cout, d.ldy = 1, tiles, kr, kr
+        d.kh, d.kw, d.stride, d.pad, d.splitk = 1, 1, 1, 0, 0
+        d.groups = fwd.ncomp
+        d.x_group_stride, d.dy_group_stride, d.dw_group_stride = tp * kc, tp * kr, cout * c
+        return d
+
     def _run_dy(self, stream=None):
         n, oh, ow, cout, ldy, cin = self.geom
-        check(_L.hnd_wino2_dy(ptr(self.dy), ptr(self.z), n, oh, ow, cout, ldy, self.tile,
-                              stream if stream is not None else stream_ptr()), 'hnd_wino2_dy')
+        check(_L.hnd_wino2_dy(ptr(self.dy), ptr(self.z), n, oh, ow, cout, ldy, self.tile, _stream(stream)), 'hnd_wino2_dy')
 
     def _run_out(self, stream=None):
         n, oh, ow, cout, ldy, cin = self.geom
         check(_L.hnd_wino2_wgrad_output_t(ptr(self.s), ptr(self.dw), cout, cin, self.tile, int(self.swapped),
-                                          stream if stream is not None else stream_ptr()), 'hnd_wino2_wgrad_output')
+                                          _stream(stream)), 'hnd_wino2_wgrad_output')
 
     def launches(self, tag):
         n, oh, ow, cout, ldy, cin = self.geom
         nc = self.ncomp
-        tiles = n * ((oh + self.tile - 1) // self.tile) * ((ow + self.tile - 1) // self.tile)
-        return [(_Step(self._run_dy, 'wino2_dy', 4 * (n * oh * ow * cout + nc * tiles * cout)), tag + '.wino_dy'),
+        return [(_Step(self._run_dy, 'wino2_dy', 4 * (n * oh * ow * cout + nc * self.tiles * cout)), tag + '.wino_dy'),
                 (self.gemm, tag),
                 (_Step(self._run_out, 'wino2_wgrad_output', 4 * (nc + 4) * cout * cin), tag + '.wino_out')]
 
@@ -1652,15 +1638,13 @@ def wino26_bnbwd_step(g, x, scale, shift, k123, relu, dgrad_conv, wgrad):
     assert tuple(x.shape) == tuple(g.shape) and tuple(dgrad_conv.geom[:4]) == (n, oh, ow, c)
     assert wgrad.geom[:3] == (n, oh, ow) and wgrad.geom[3] == c and wgrad.geom[4] == c
     pad = dgrad_conv.pad
-    tiles_d = n * ((oh + 2 * pad - 1 + 5) // 6) * ((ow + 2 * pad - 1 + 5) // 6)
-    tiles_w = n * ((oh + 5) // 6) * ((ow + 5) // 6)
 
     def fn(stream=None):
         check(_L.hnd_wino26_bnbwd_transforms(ptr(g), ptr(x), ptr(scale), ptr(shift), ptr(k123), int(relu), n, oh, ow, c,
-                                             pad, ptr(dgrad_conv.v), ptr(wgrad.z),
-                                             stream if stream is not None else stream_ptr()),
+                                             pad, ptr(dgrad_conv.v), ptr(wgrad.z), _stream(stream)),
               'hnd_wino26_bnbwd_transforms')
-    step = _Step(fn, 'wino2_bnbwd_fused', 4 * (2 * n * oh * ow * c + 49 * (tiles_d + tiles_w) * c))
+    # reads g and x, writes the 49 components of both launches' real tiles (over the same dy: the asserts above)
+    step = _Step(fn, 'wino2_bnbwd_fused', 4 * (2 * n * oh * ow * c + 49 * (dgrad_conv.tiles + wgrad.tiles) * c))
     step.keep = (g, x, scale, shift, k123, dgrad_conv, wgrad)
     return step
 
